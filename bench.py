@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the UniDepthV2 infer() hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, measures the one-call p50 latency that the metric names, and prints the result
+line.  Everything else (MFMA calibration, per-kernel roofline, the rccl report, the other configs, the CPU baselines) runs only with
+`--full`.  `--dump-outputs DIR` writes the outputs of the last timed step as DIR/<name>.npy (see dump_outputs).
 
 `--gpus N` with N > 1 and no torch.distributed environment: bench.py re-launches itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU, RCCL); when the
@@ -18,6 +22,7 @@ value = N * 8 images * K / max-over-ranks wall time.
 One JSON line on rank 0 with the driver contract fields plus
   value_one_call / p50_latency_ms -- the same workload with ONE infer() in flight (the headline `value` keeps `--inflight`
                   (default 2) independent calls in flight per GPU: throughput mode for a stream of requests);
+and, with --full only:
   roofline     -- the dominant kernel class of the step (an MFMA GEMM instantiation, named as rocprofv3 prints it): algorithmic
                   FLOP per launch / average launch duration measured live with HIP events on the launch stream, against the
                   2.5 PFLOP/s dense fp16 peak; algorithmic bytes per launch (operands + outputs once); `traffic` = HBM bytes per
@@ -75,9 +80,40 @@ def parse_args(argv=None):
     ap.add_argument("--gather", default="depth,confidence,intrinsics")
     ap.add_argument("--gather-algo", default="collective", choices=["collective", "direct"],
                     help="exchange step: RCCL all_gather_into_tensor, or the all-pairs send/recv group (unidepth_amd.dist.all_gather_direct)")
-    ap.add_argument("--dump-ops", default="", help="write per-launch timings (tsv) to this file")
+    ap.add_argument("--dump-ops", default="", help="write per-launch timings (tsv) to this file (with --full)")
     ap.add_argument("--inflight", type=int, default=2, help="infer() calls in flight per GPU during the timed steps (1 = one call at a time)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32; at most 64 MB in all, larger outputs as a seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: MFMA calibration, per-kernel roofline, rccl report, other configs, CPU baselines")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 60 << 20        # below the 64 MB the comparison of two builds allows
+
+
+def dump_outputs(out, path, seed=0):
+    """Write every output of one infer() call as `path`/<name>.npy (float32, float64 kept as is).  Outputs are taken whole while they
+    fit an even share of DUMP_BUDGET_BYTES left for them (smallest first); a larger one is written as the flattened values at a fixed
+    seeded set of sorted indices, the same for the same shapes, so two builds run with the same arguments compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for k, v in out.items():
+        a = v.detach().cpu()
+        arrays[k] = (a.double() if a.dtype == torch.float64 else a.float()).numpy()
+    left = DUMP_BUDGET_BYTES
+    names = sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+    for i, k in enumerate(names):
+        a = arrays[k]
+        share = left // (len(names) - i)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
 
 
 def _free_port() -> int:
@@ -198,6 +234,8 @@ def main():
             gather(out)
         return out
 
+    last_out = {}
+
     def timed(n, with_gather=True):
         pipe.sync()
         torch.cuda.synchronize()
@@ -206,8 +244,9 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(n):
-            step(with_gather)
+            out = step(with_gather)
         pipe.sync()
+        last_out["out"] = out
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -221,10 +260,12 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    calib = mfma_attainable(torch, dev) if (rank == 0 and not args.no_kernel_timing) else None     # after the warm-up (clocks up), before the timed region
+    calib = mfma_attainable(torch, dev) if (args.full and rank == 0 and not args.no_kernel_timing) else None     # after the warm-up (clocks up), before the timed region
     for _ in range(2):
         step()
     elapsed = timed(args.steps)                      # THE timed region: exactly K steps, barrier + synchronize on both sides, max over ranks
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out["out"], args.dump_outputs)
     # latency of ONE call with nothing else in flight (outside the timed region)
     lat = []
     for _ in range(max(30, min(args.steps, 50))):
@@ -251,7 +292,7 @@ def main():
                    "global_batch": world * B, "parallelism": f"dp{world}" + (f" + RCCL all-gather({','.join(gather_keys)})" if world > 1 else "")},
     }
 
-    if world > 1:
+    if world > 1 and args.full:
         result["rccl"] = rccl_report(torch, dist, model, rgb, gather, timed, args, world, rank, dev, backend, B, ms_per_step)
         result["rccl"]["exchange_route"] = exchange_route["note"]
     if rank == 0:
@@ -260,17 +301,17 @@ def main():
         # the metric is "images/sec + p50 latency": both halves also inside `config` / `roofline`, the objects every consumer of the line keeps
         result["config"].update({"value_one_call": result["value_one_call"], "p50_latency_ms": result["p50_latency_ms"],
                                  "p90_latency_ms": result["p90_latency_ms"], "inflight": result["inflight"]})
-        if not args.no_kernel_timing:
+        if args.full and not args.no_kernel_timing:
             result.update(kernel_timing(torch, model, fl, B, args.dump_ops, calib))
             scope = result["roofline_enc_attention_mlp"]
             result["roofline"].update({"scope_frac": scope["frac"], "scope_achieved": scope["achieved"], "scope_ms_per_step": scope["ms_per_step"],
                                        "scope": "encoder attention + MLP blocks (north_star target 0.60): see roofline_enc_attention_mlp",
                                        "one_call_p50_ms": result["p50_latency_ms"], "one_call_images_per_s": result["value_one_call"]})
-        if world == 1 and not args.no_extra_configs and args.arch == "vitl14" and tuple(args.size) == (518, 518):
+        if args.full and world == 1 and not args.no_extra_configs and args.arch == "vitl14" and tuple(args.size) == (518, 518):
             del pipe
             model.clear_plans()
             result["configs"] = extra_configs(torch, model, dev, cpu=not args.no_cpu_baseline)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(torch, cfg, sd, H, W)
         print(json.dumps(result))
     if world > 1:
