@@ -464,6 +464,24 @@ typedef struct UdExtractPatches {
   int B, C, H, W, N, h, w, pad_h, pad_w;
 } UdExtractPatches;
 int ud_extract_patches(const UdExtractPatches* desc, void* stream);
+/* 2-D depth metrics of a batch: replaces utils/evaluation_depth.py eval_depth (its DICT_METRICS applied per image after the bilinear
+ * resample of the predictions), as a few stream-ordered launches with no host synchronisation (csrc/evaldepth.hip).
+ *   gt fp32 [B,H,W]; pred fp32 [B,h,w] (bilinear align_corners=False to H x W, source index clamped at 0; identity when h = H and w = W);
+ *   mask u8 [B,H,W] (nonzero = valid) or NULL (every pixel valid); has_max_depth != 0 also drops pixels with !(g <= max_depth).
+ *   thresholds fp32 [200]: the 100 d_auc thresholds 1.25^e_k (non-decreasing), then the 100 exponents e_k (the trapezoid abscissae).
+ *   out fp32 [18,B] in the reference's key order: d1_ssi d1_si d1 d2 d3 rmse rmselog arel_ssi arel_si arel sqrel log10 silog medianlog
+ *   d_auc tau_ssi tau_si tau; an image with no valid pixel gives NaN in every row.
+ *   work: device scratch of at least ud_eval_depth_work_bytes(B, H, W) bytes (host-only query), work_bytes its size.
+ *   Bitwise reproducible: fp64 sums reduced in a fixed order, integer atomics only. */
+typedef struct UdEvalDepth {
+  const float* gt; const float* pred; const unsigned char* mask; const float* thresholds;
+  float* out; void* work;
+  int B, H, W, h, w;
+  float max_depth; int has_max_depth;
+  long long work_bytes;
+} UdEvalDepth;
+int ud_eval_depth(const UdEvalDepth* desc, void* stream);
+long long ud_eval_depth_work_bytes(int B, int H, int W);
 
 /* ---- launch programs: a recorded list of the ops above replayed with one call (host-side runtime) ---- */
 typedef struct UdProgram UdProgram;
@@ -505,7 +523,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 /* the same for v_mfma_f32_16x16x32_f16 (the GEMM family's instruction): workgroups of 8 waves, sink >= workgroups * 512 floats (round 6) */
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
-/* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13) */
+/* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14) */
 int ud_version(void);
 int ud_struct_size(int which);
 const char* ud_last_error(void);

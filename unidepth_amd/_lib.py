@@ -81,6 +81,12 @@ class UdExtractPatches(C.Structure):
                 ("h", i32), ("w", i32), ("pad_h", i32), ("pad_w", i32)]
 
 
+class UdEvalDepth(C.Structure):
+    _fields_ = [("gt", vp), ("pred", vp), ("mask", vp), ("thresholds", vp), ("out", vp), ("work", vp),
+                ("B", i32), ("H", i32), ("W", i32), ("h", i32), ("w", i32), ("max_depth", f32), ("has_max_depth", i32),
+                ("work_bytes", i64)]
+
+
 (UD_V1_RESIZE_AA, UD_V1_SH_EMBED, UD_V1_SOFTMAX, UD_V1_ATTN_FEWQ, UD_V1_HEAD_MIX) = range(1, 6)
 (UD_V1_ADD, UD_V1_COPY_ROWS) = (8, 9)
 (UD_V1_CAMERA, UD_V1_POINTS, UD_V1_MEAN3, UD_V1_PREPROCESS, UD_V1_VIT_TAP) = range(11, 16)
@@ -187,6 +193,7 @@ def _load():
         "ud_knn_points": [P(UdKnn), vp],
         "ud_knn_split": [P(UdKnn)],
         "ud_extract_patches": [P(UdExtractPatches), vp],
+        "ud_eval_depth": [P(UdEvalDepth), vp],
         "ud_program_run": [vp, i32, i32, vp],
         "ud_calib_mfma_stream": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
         "ud_calib_mfma_stream16": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
@@ -201,7 +208,9 @@ def _load():
     lib.ud_program_create.restype = vp
     lib.ud_last_error.argtypes = []
     lib.ud_last_error.restype = C.c_char_p
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead]):
+    lib.ud_eval_depth_work_bytes.argtypes = [i32, i32, i32]
+    lib.ud_eval_depth_work_bytes.restype = i64
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth]):
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)
         if lib.ud_struct_size(i) != C.sizeof(st):

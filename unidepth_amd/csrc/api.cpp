@@ -29,6 +29,7 @@ extern "C" int ud_struct_size(int which) {
     case 11: return (int)sizeof(UdKnn);
     case 12: return (int)sizeof(UdExtractPatches);
     case 13: return (int)sizeof(UdCameraHead);
+    case 14: return (int)sizeof(UdEvalDepth);
     default: return -1;
   }
 }

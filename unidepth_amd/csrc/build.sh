@@ -19,6 +19,8 @@ done
 # evaluation-side kernels: bit-exact fp32 distances (separately rounded multiply and add, like the reference's CPU build), so no FMA
 # contraction anywhere in this file (the in-source pragma does not reach ext_vector_type arithmetic)
 ( hipcc $FLAGS -ffp-contract=off "$@" -c evalops.hip -o $BD/evalops.o ) & pids+=($!)
+# 2-D depth metrics: the resample weights, ratios and rescales must round every operation separately (threshold counts), same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c evaldepth.hip -o $BD/evaldepth.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)

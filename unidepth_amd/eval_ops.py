@@ -3,10 +3,12 @@
     knn_points, knn_gather          unidepth/ops/knn/functions/knn.py:113-196, 199-249  (forward; the KNN extension)
     ChamferDistance, chamfer_dist   unidepth/utils/chamfer_distance.py:60-159, unidepth/utils/evaluation_depth.py:12-18
     auc, f1_score, DICT_METRICS_3D, eval_3d   unidepth/utils/evaluation_depth.py:21-34,74-91,109-125,160-182 (the 3-D metrics)
+    eval_depth, DICT_METRICS, DICT_METRICS_D  unidepth/utils/evaluation_depth.py:37-72,93-110,124-147 (the 2-D depth metrics)
     RandomPatchExtractor            unidepth/ops/extract_patches/modules/patch_extractor.py:10-42 (forward)
 
 Same names, argument meaning and error behaviour; inference / evaluation only (no autograd: the reference's backward kernels are
-training code).  Tensors must live on the GPU: there is no CPU path."""
+training code).  Tensors must live on the GPU: there is no CPU path.  eval_depth / DICT_METRICS compute in fp32 whatever the input
+dtype (the reference computes in the input dtype), and run in ud_eval_depth without any host synchronisation."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -197,3 +199,91 @@ class RandomPatchExtractor(torch.nn.Module):
                pad_h=pad_h, pad_w=pad_w)
         check(_lib.lib.ud_extract_patches(d, cur_stream()), "ud_extract_patches")
         return out.to(dtype)
+
+
+# ---- 2-D depth metrics (utils/evaluation_depth.py eval_depth, DICT_METRICS, DICT_METRICS_D) ----------------------------------------
+
+EVAL_DEPTH_KEYS = ("d1_ssi", "d1_si", "d1", "d2", "d3", "rmse", "rmselog", "arel_ssi", "arel_si", "arel", "sqrel", "log10", "silog",
+                   "medianlog", "d_auc", "tau_ssi", "tau_si", "tau")          # the reference's dict order = the rows of ud_eval_depth's out
+_DAUC = {}
+
+
+def _dauc_thresholds(device) -> torch.Tensor:
+    """[1.25 ** e, e] for e = linspace(0.01, 5.0, 100) in fp32, made by torch on the device as the reference makes them; once per device."""
+    key = (device.type, device.index)
+    if key not in _DAUC:
+        e = torch.linspace(0.01, 5.0, steps=100, device=device)
+        _DAUC[key] = torch.cat([1.25 ** e, e]).contiguous()
+    return _DAUC[key]
+
+
+def _eval_depth_rows(gt: torch.Tensor, pred: torch.Tensor, mask: Optional[torch.Tensor], max_depth) -> torch.Tensor:
+    """ud_eval_depth on fp32 gt [B,H,W], pred [B,h,w], u8 mask [B,H,W] or None -> fp32 [18, B] (rows in EVAL_DEPTH_KEYS order)."""
+    B, H, W = gt.shape
+    h, w = pred.shape[1:]
+    dev = gt.device
+    nbytes = int(_lib.lib.ud_eval_depth_work_bytes(B, H, W))
+    if nbytes < 0:
+        raise ValueError(f"eval_depth: unsupported sizes B={B} H={H} W={W}")
+    work = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    out = torch.empty(len(EVAL_DEPTH_KEYS), B, device=dev, dtype=torch.float32)
+    d = mk(_lib.UdEvalDepth, gt=gt, pred=pred, mask=mask, thresholds=_dauc_thresholds(dev), out=out, work=work, B=B, H=H, W=W, h=h, w=w,
+           max_depth=0.0 if max_depth is None else float(max_depth), has_max_depth=0 if max_depth is None else 1, work_bytes=nbytes)
+    check(_lib.lib.ud_eval_depth(d, cur_stream()), "ud_eval_depth")
+    return out
+
+
+def eval_depth(gts: torch.Tensor, preds: torch.Tensor, masks: torch.Tensor, max_depth=None):
+    """Per-image depth metrics of a batch (utils/evaluation_depth.py:132-147): gts [B,1,H,W], preds [B,1,h,w] (bilinearly resampled to
+    H x W, align_corners=False), masks [B,1,H,W] bool; valid pixels = mask & (gt <= max_depth when given).  Returns the reference's 18
+    keys in its order, each a [B] fp32 GPU tensor: d1..d3, rmse, rmselog, arel, sqrel, log10, silog, medianlog, d_auc, tau on the
+    prediction, and d1 / arel / tau again after the least-squares scale-and-shift (_ssi) and the median scale (_si) alignment.  An
+    image without a valid pixel gives NaN everywhere, as in the reference.  One ud_eval_depth call: no host synchronisation, bitwise
+    reproducible.  Inputs of another float dtype are converted to fp32 first (the reference computes in the input dtype)."""
+    for name, t in (("gts", gts), ("preds", preds), ("masks", masks)):
+        if not isinstance(t, torch.Tensor) or t.ndim != 4 or t.shape[1] != 1:
+            raise ValueError(f"eval_depth: {name} must be [B,1,H,W], got {tuple(getattr(t, 'shape', ()))}")
+    B = gts.shape[0]
+    if B == 0:
+        raise ValueError("eval_depth: empty batch")
+    if preds.shape[0] != B or masks.shape[0] != B:
+        raise ValueError(f"eval_depth: batch sizes differ (gts {B}, preds {preds.shape[0]}, masks {masks.shape[0]})")
+    if masks.shape != gts.shape:
+        raise ValueError(f"eval_depth: masks {tuple(masks.shape)} must match gts {tuple(gts.shape)}")
+    H, W = gts.shape[-2:]
+    if H * W > 0 and preds.shape[-2] * preds.shape[-1] == 0:
+        raise ValueError("eval_depth: empty prediction")
+    if not (gts.is_cuda and preds.is_cuda and masks.is_cuda):
+        raise RuntimeError("eval_depth: GPU tensors expected (the HIP kernels are the only implementation)")
+    gt = gts.reshape(B, H, W).float().contiguous()
+    pred = preds.reshape(B, preds.shape[-2], preds.shape[-1]).float().contiguous()
+    mask = masks.reshape(B, H, W).to(torch.bool).contiguous().view(torch.uint8)
+    out = _eval_depth_rows(gt, pred, mask, max_depth)
+    return {name: out[k] for k, name in enumerate(EVAL_DEPTH_KEYS)}
+
+
+def _metric_1d(name: str):
+    row = EVAL_DEPTH_KEYS.index(name)
+
+    def fn(gt: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
+        if gt.ndim != 1 or pred.shape != gt.shape:
+            raise ValueError(f"DICT_METRICS[{name!r}]: 1-D gt and pred of equal length expected")
+        if not (gt.is_cuda and pred.is_cuda):
+            raise RuntimeError(f"DICT_METRICS[{name!r}]: GPU tensors expected (the HIP kernels are the only implementation)")
+        n = gt.shape[0]
+        out = _eval_depth_rows(gt.float().contiguous().view(1, 1, n), pred.float().contiguous().view(1, 1, n), None, None)
+        return out[row, 0]
+
+    fn.__name__ = name
+    return fn
+
+
+# utils/evaluation_depth.py:93-110: metric(gt, pred) on the 1-D valid pixels of one image -> 0-d tensor; each is one image of 1 x n
+# through ud_eval_depth (no mask, no resample)
+DICT_METRICS = {name: _metric_1d(name) for name in ("d1", "d2", "d3", "rmse", "rmselog", "arel", "sqrel", "log10", "silog", "medianlog",
+                                                    "d_auc", "tau")}
+
+DICT_METRICS_D = {           # utils/evaluation_depth.py:124-129: per-pixel maps (plain torch, not on a hot path)
+    "a1": lambda gt, pred: (torch.maximum((gt / pred), (pred / gt)) > 1.25 ** 1.0).to(torch.float32),
+    "abs_rel": lambda gt, pred: (torch.abs(gt - pred) / gt),
+}
