@@ -10,6 +10,15 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _dry_run():
+    """tests/dry_run.py: the host recording context and the models with host-packed weights."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("dry_run", os.path.join(ROOT, "tests", "dry_run.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def test_library_exports_header_symbols():
     import ctypes
     from unidepth_amd import _lib
@@ -452,31 +461,24 @@ def test_engine_classes_are_nn_modules(tmp_path):
     assert isinstance(v1, torch.nn.Module) and v1.eval() is v1 and v1.device.type == "cpu"
 
 
-def test_v1_plan_builder_dry_run_validates_every_gemm_descriptor(monkeypatch):
+def test_v1_plan_builder_dry_run_validates_every_gemm_descriptor():
     """The launch program of a UniDepthV1 infer() is RECORDED on the host (host tensors stand in for the device buffers, nothing runs) and
     every GEMM descriptor it records is handed to ud_gemm_f16: without a GPU the call must get past the C side's argument validation
     (wrap / K / Cin / stride rules, include/unidepth_hip.h UdGemm) and fail only at the launch itself -- a builder bug (e.g. a three-term
     weight against a two-term A stride) is caught here, not on the GPU box."""
-    import contextlib
-    from oracle import synth_v1
-    from unidepth_amd import UniDepthV1, _lib, ops, unidepthv1 as U
+    from unidepth_amd import _lib
     if torch.cuda.is_available():
         pytest.skip("host-only dry run")
-    cfg = synth_v1.load_config_v1("cnvnxtl")
-    m = UniDepthV1(cfg).load_state_dict(synth_v1.make_synthetic_checkpoint_v1(cfg, 301))
-    dev = torch.device("cpu")
-    m._w = {**U.pack_convnext(cfg, m._sd, dev), **U.pack_v1_decoder(cfg, m._sd, dev)}
-    m._device = dev
-    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
-    monkeypatch.setattr(ops, "ptr", lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr()))
-    real_add, seen = _lib.lib.ud_program_add_gemm, []
+    dry = _dry_run()
+    m = dry.v1_model("cnvnxtl", 301)
+    seen = []
 
-    def add(h, dref):
+    def add(real_add, h, dref):
         rc = _lib.lib.ud_gemm_f16(dref, None)
         seen.append((rc, _lib.lib.ud_last_error().decode() if rc else "", dref._obj.M, dref._obj.N, dref._obj.K, dref._obj.a_wrap, dref._obj.Cin))
         return real_add(h, dref)
-    monkeypatch.setattr(ops.lib, "ud_program_add_gemm", add)
-    plan = m._full_plan(1, 240, 320, True, False, True, 0, False)
+    with dry.host_recording({"gemm": add}):
+        plan = m._full_plan(1, 240, 320, True, False, True, 0, False)
     assert len(plan.prog) > 300 and len(seen) > 150      # (round 5: the NystromBlocks lost their ~90 landmark / pseudo-inverse launches)
     bad = [r for r in seen if r[0] != -2]                     # -2 = UD_ERR_LAUNCH (include/unidepth_hip.h)
     assert not bad, bad[:3]                                    # UD_ERR_BAD_ARG would mean a descriptor the kernels refuse
@@ -488,28 +490,19 @@ def test_v2_plan_builder_dry_run_order_and_descriptors(monkeypatch):
     """The UniDepthV2 launch program recorded on the host (nothing runs): every GEMM descriptor passes the C side's argument validation, and
     the decoder starts with the grouped feature adapters, then the camera head + rays + ray embedding, then LayerNorm / q projection and the
     K / V projection of the ray embedding."""
-    import contextlib
-    from oracle import synth
-    from unidepth_amd import UniDepthV2, _lib, ops
-    from unidepth_amd.weights import pack
+    from unidepth_amd import _lib, ops
     if torch.cuda.is_available():
         pytest.skip("host-only dry run")
-    cfg = synth.load_config("vits14")
-    m = UniDepthV2(cfg).load_state_dict(synth.make_synthetic_checkpoint(cfg, 3))
-    dev = torch.device("cpu")
-    m._w = pack(cfg, m._sd, dev)
-    m._device = dev
-    m.resolution_level = 2
-    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
-    monkeypatch.setattr(ops, "ptr", lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr()))
-    real_add, seen = _lib.lib.ud_program_add_gemm, []
+    dry = _dry_run()
+    m = dry.v2_model("vits14", 3, 2)
+    seen = []
 
-    def add(h, dref):
+    def add(real_add, h, dref):
         rc = _lib.lib.ud_gemm_f16(dref, None)
         seen.append((rc, _lib.lib.ud_last_error().decode() if rc else ""))
         return real_add(h, dref)
-    monkeypatch.setattr(ops.lib, "ud_program_add_gemm", add)
-    plan = m._plan(1, 462, 616, 0, True, True)
+    with dry.host_recording({"gemm": add}):
+        plan = m._plan(1, 462, 616, 0, True, True)
     assert len(seen) > 60 and not [r for r in seen if r[0] != -2], [r for r in seen if r[0] != -2][:3]     # -2 = UD_ERR_LAUNCH: arguments accepted
     tags = [t[1] for t in plan.prog.meta]
     i0 = tags.index("dec.adapters(x4)")
@@ -521,7 +514,8 @@ def test_v2_plan_builder_dry_run_order_and_descriptors(monkeypatch):
     # outside the one-launch kernel's limits the same layers are recorded one by one (4 adapters, 14 Linears, 6 LayerNorms, 2 attentions: 26 launches)
     monkeypatch.setattr(ops, "camera_head_supported", lambda d: False)
     m.clear_plans()
-    plan2 = m._plan(1, 462, 616, 0, True, True)
+    with dry.host_recording({"gemm": add}):
+        plan2 = m._plan(1, 462, 616, 0, True, True)
     tags2 = [t[1] for t in plan2.prog.meta]
     cam2 = tags2[tags2.index("dec.adapters(x4)") + 1:tags2.index("ray_embed") + 1]
     assert "cam.head" not in cam2 and cam2.count("cam.adapter") == 4 and cam2.count("attention_small") == 2

@@ -2,7 +2,6 @@
 descriptor that the V2 (vits14, vitl14) and V1 (cnvnxtl) launch programs record on the host falls into a class the GPU module covers, so
 a product path cannot appear without a guarded GPU test.  Nothing runs on a device: the plans are recorded with host tensors standing in
 for the device buffers (the dry runs of tests/test_host_cpu.py)."""
-import contextlib
 import ctypes as C
 import importlib.util
 import os
@@ -13,39 +12,26 @@ import torch
 _spec = importlib.util.spec_from_file_location("test_kernel_layouts_gpu", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_kernel_layouts_gpu.py"))
 lay = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(lay)
+_spec = importlib.util.spec_from_file_location("dry_run", os.path.join(os.path.dirname(os.path.abspath(__file__)), "dry_run.py"))
+dry_run = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(dry_run)
 
 PLANS = (("v2", "vits14"), ("v2", "vitl14"), ("v1", "cnvnxtl"))
 
 
-def _record(monkeypatch, kind, arch):
-    from unidepth_amd import _lib, ops
+def _record(kind, arch):
     seen = {k: [] for k in ("gemm", "linear_f32", "layernorm", "attention")}
-    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
-    monkeypatch.setattr(ops, "ptr", lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr()))
-    for name in seen:
-        real = getattr(_lib.lib, "ud_program_add_" + name)
 
-        def add(h, dref, real=real, name=name):
+    def log(name):
+        def add(real, h, dref):
             seen[name].append(type(dref._obj).from_buffer_copy(dref._obj))
             return real(h, dref)
-        monkeypatch.setattr(ops.lib, "ud_program_add_" + name, add)
-    dev = torch.device("cpu")
-    if kind == "v2":
-        from oracle import synth
-        from unidepth_amd import UniDepthV2
-        from unidepth_amd.weights import pack
-        cfg = synth.load_config(arch)
-        m = UniDepthV2(cfg).load_state_dict(synth.make_synthetic_checkpoint(cfg, 3))
-        m._w, m._device, m.resolution_level = pack(cfg, m._sd, dev), dev, 2
-        m._plan(1, 462, 616, 0, True, True)
-    else:
-        from oracle import synth_v1
-        from unidepth_amd import UniDepthV1, unidepthv1 as U
-        cfg = synth_v1.load_config_v1(arch)
-        m = UniDepthV1(cfg).load_state_dict(synth_v1.make_synthetic_checkpoint_v1(cfg, 301))
-        m._w, m._device = {**U.pack_convnext(cfg, m._sd, dev), **U.pack_v1_decoder(cfg, m._sd, dev)}, dev
-        m._full_plan(1, 240, 320, True, False, True, 0, False)
-    monkeypatch.undo()
+        return add
+    with dry_run.host_recording({name: log(name) for name in seen}):
+        if kind == "v2":
+            dry_run.v2_model(arch, 3, 2)._plan(1, 462, 616, 0, True, True)
+        else:
+            dry_run.v1_model(arch, 301)._full_plan(1, 240, 320, True, False, True, 0, False)
     return seen
 
 
@@ -53,11 +39,7 @@ def _record(monkeypatch, kind, arch):
 def recorded():
     if torch.cuda.is_available():
         pytest.skip("host-only dry run")
-    mp = pytest.MonkeyPatch()
-    try:
-        return {f"{k}/{a}": _record(mp, k, a) for k, a in PLANS}
-    finally:
-        mp.undo()
+    return {f"{k}/{a}": _record(k, a) for k, a in PLANS}
 
 
 def test_gemm_cases_reach_the_schedule_they_name():

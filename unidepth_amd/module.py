@@ -18,6 +18,9 @@ meaning instead of an AttributeError:
 """
 from __future__ import annotations
 
+import collections
+import json
+import os
 import warnings
 
 import torch
@@ -37,14 +40,18 @@ class EngineModule(torch.nn.Module, _HubMixin):
         super().__init__()
         self.training = False
         self._device = torch.device("cpu")
+        self._sd = None                                   # the reference's state_dict, fp32 on the host
+        self._w = None                                    # packed device weights (_ensure_packed)
+        self._plans: "collections.OrderedDict" = collections.OrderedDict()   # LRU of recorded plans, most recent last; bound: self.max_plans
 
     # ---- device / dtype ------------------------------------------------------------------------------------------------
     @property
     def device(self):
         return self._device
 
-    def _move(self, device: torch.device) -> None:       # subclasses drop their packed weights / plans here
-        raise NotImplementedError
+    def _move(self, device: torch.device) -> None:       # packed weights and plans belong to a device (and to the weights: load_state_dict)
+        self._w = None
+        self._plans.clear()
 
     def to(self, *args, **kwargs):
         device = kwargs.get("device")
@@ -110,7 +117,72 @@ class EngineModule(torch.nn.Module, _HubMixin):
         """`model(rgb, camera)` runs infer(): the reference's training-time forward(inputs, image_metas) has no counterpart here."""
         return self.infer(*args, **kwargs)
 
-    # ---- weights ---------------------------------------------------------------------------------------------------------
+    # ---- weights (HF mixin layout: config.json + model.safetensors / pytorch_model.bin) -----------------------------------
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path: str, **kwargs):
+        path = str(pretrained_model_name_or_path)
+        if not os.path.isdir(path):
+            from huggingface_hub import snapshot_download     # e.g. "lpiccinelli/unidepth-v2-vitl14" (needs network / cache)
+            path = snapshot_download(path, allow_patterns=["config.json", "model.safetensors", "pytorch_model.bin"])
+        with open(os.path.join(path, "config.json")) as f:
+            config = json.load(f)
+        model = cls(config)
+        st = os.path.join(path, "model.safetensors")
+        if os.path.exists(st):
+            from safetensors.torch import load_file
+            sd = load_file(st)
+        else:
+            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
+        return model.load_state_dict(sd)
+
+    def load_state_dict(self, state_dict: dict, strict: bool = False):
+        if "model" in state_dict and not torch.is_tensor(state_dict["model"]):
+            state_dict = state_dict["model"]                                            # unidepthv2.py:386-388, unidepthv1.py:381-385
+        self._sd = {k.replace("module.", ""): v.detach().float().cpu() for k, v in state_dict.items()}
+        self._move(self._device)                          # everything derived from the old weights goes
+        return self
+
+    def _pack(self) -> dict:                              # subclasses: the packed device weights of self._sd
+        raise NotImplementedError
+
+    def _ensure_packed(self):
+        if self._device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} (MI355X engine) runs on a ROCm GPU only: call .to('cuda') first; there is no CPU path")
+        if self._sd is None:
+            raise RuntimeError("no weights loaded (use from_pretrained or load_state_dict)")
+        if self._w is None:
+            with torch.cuda.device(self._device):
+                self._w = self._pack()
+
+    # ---- plan cache ------------------------------------------------------------------------------------------------------
+    def _cached_plan(self, key, build):
+        """The plan cached under `key`, or `build()` (under the model's device).  A plan owns the full activation set of its signature
+        (~2.6 GB for ViT-L at bs=8): the cache is an LRU of `max_plans` entries, so a stream of many image shapes (KITTI / nuScenes
+        style) cannot grow device memory without bound."""
+        plan = self._plans.get(key)
+        if plan is not None:
+            self._plans.move_to_end(key)
+            return plan
+        self._evict_plans(max(1, self.max_plans) - 1)
+        with torch.cuda.device(self._device):
+            plan = build()
+        self._plans[key] = plan
+        return plan
+
+    def _evict_plans(self, keep: int):
+        """Evict least-recently-used plans down to `keep`.  An evicted plan's buffers go back to the caching allocator of whatever stream
+        allocated them, while its launch program may still be queued on ANOTHER stream (pipeline slots): drain the device first -- rare,
+        and a plan rebuild costs far more than this sync."""
+        if len(self._plans) > keep:
+            if self._device.type == "cuda":
+                torch.cuda.synchronize(self._device)
+            while len(self._plans) > keep:
+                self._plans.popitem(last=False)
+
+    def clear_plans(self):
+        """Drop every cached launch plan (device activation buffers of all signatures seen so far; rebuilt on the next call)."""
+        self._evict_plans(0)
+
     def state_dict(self, *args, **kwargs):
         """fp32 tensors under the reference's key names (exactly what load_state_dict received, `module.` prefixes stripped)."""
         sd = getattr(self, "_sd", None)

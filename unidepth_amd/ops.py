@@ -38,6 +38,11 @@ def mk(struct, **kw):
     return d
 
 
+def gemm_pick(**kw) -> int:
+    """The schedule ud_gemm_f16 would run this descriptor on (include/unidepth_hip.h ud_gemm_pick).  Host-side, nothing is launched."""
+    return lib.ud_gemm_pick(C.byref(mk(UdGemm, **kw)))
+
+
 def camera_head_desc(phases, T, H, Cc, scale, eps, sync_ws, workgroups=0, fail_host=None, spin_limit=0):
     """UdCameraHead from a list of phase dicts (UdCamPhase fields; tensors become device pointers, an int is a raw address)."""
     d = UdCameraHead()
