@@ -53,6 +53,42 @@ extern "C" {
  * layers/attention.py:117-122,139; layers/mlp.py:30-33; decoder.py:44,145), the patch-embed Conv2d
  * (metadinov2/patch_embed.py:66-88), ConvTranspose2d (decoder.py:166-173), 3x3/1x1 Conv2d
  * (layers/upsample.py:148-163,208-214; decoder.py:199-226) as implicit GEMMs. */
+/* UdGemm.tile_hint.  A forced schedule that is not eligible for the descriptor falls back as noted; 4 and values above 14 are unassigned. */
+#define UD_HINT_AUTO 0            /* the cost model decides (csrc/gemm.hip route()) */
+#define UD_HINT_TILE128 1         /* 128-row tiles only: no large-tile, no halo-tile schedule */
+#define UD_HINT_LIST256 2         /* 256 x 256 tile list */
+#define UD_HINT_LIST192 3         /* 192 x 256 tile list (dense A: with the 3-deep weight ring) */
+#define UD_HINT_PLAIN128 5        /* 128 x 128 tiles, plain 2-stage kernel */
+#define UD_HINT_RING 6            /* 128 x 128 tiles, 4-stage pipelined ring without the K split (what auto picks when the tile count is at most
+                                   * the CU count and K >= 512) */
+#define UD_HINT_RING_SPLITK 7     /* 6 + the two-way K split across CUs (splitk_ws / splitk_cnt; K >= 512 instead of auto's 1024) */
+#define UD_HINT_BALANCED 8        /* row-balanced schedule of the 256-column kernel (auto picks it when the tile list would leave the last round
+                                   * partly empty); not eligible -> auto */
+#define UD_HINT_LIST192_W2 9      /* 192 x 256 tile list with the 2-deep weight ring (dense 192-row launches otherwise fetch the weight operand two
+                                   * K-tiles ahead through a 3-deep LDS ring: same bits, the weights of a layer are cold in every step) */
+#define UD_HINT_LIST192_SPLITK 10 /* 192 x 256 tiles with the two-way K split of the large-tile list (splitk_ws_bytes); refused -> 128-row tiles */
+#define UD_HINT_PINGPONG 11       /* 192 x 256 tiles in the ping-pong form (csrc/gemm_pp.hip; UD_EPI_F32, dense); refused -> 192 x 256 tile list */
+#define UD_HINT_DUO_FIRST 12      /* 192 x 128 tiles, two workgroups per CU (csrc/gemm_pp.hip), the first-dispatched workgroup of a CU at high priority; */
+#define UD_HINT_DUO_EQUAL 13      /*   the same with equal priorities; */
+#define UD_HINT_DUO_SECOND 14     /*   the same with the second-dispatched one at high priority.  Refused -> 192 x 256 tile list */
+
+/* ud_gemm_pick: one schedule code, plus the two flags for the large-tile instantiations */
+#define UD_PICK_TILE128 0         /* 128-row tiles, 128 columns (plain 2-stage kernel) */
+#define UD_PICK_TILE128_BN64 1    /*   64 columns (32 < N <= 64) */
+#define UD_PICK_TILE128_BN32 2    /*   32 columns (N <= 32) */
+#define UD_PICK_LIST192 3         /* 192 x 256 tile list */
+#define UD_PICK_LIST256 4         /* 256 x 256 tile list */
+#define UD_PICK_CONV_TILE 5       /* halo-tile 3x3 convolution (either head-conv kernel) */
+#define UD_PICK_RING 6            /* 128 x 128 tiles, 4-stage pipelined ring */
+#define UD_PICK_RING_SPLITK 7     /*   with the two-way K split across CUs */
+#define UD_PICK_BALANCED 8        /* row-balanced schedule of the 256-column kernel */
+#define UD_PICK_LIST192_SPLITK 10 /* 192 x 256 tiles with the two-way K split */
+#define UD_PICK_PINGPONG 11       /* 192 x 256 tiles, ping-pong form */
+#define UD_PICK_DUO 12            /* 192 x 128 tiles, two workgroups per CU */
+#define UD_PICK_SCHEDULE 15       /* mask of the schedule code */
+#define UD_PICK_LN_CONSUMER 16    /* flag: the folded-LayerNorm consumer instantiation runs (row_stats_in) */
+#define UD_PICK_GROUPED 32        /* flag: a grouped problem runs as ONE large-tile launch */
+
 typedef struct UdGemm {
   const void* A;
   const void* W;
@@ -81,14 +117,7 @@ typedef struct UdGemm {
   int groups;
   long long gA, gW, gBias, gOut, gOut2, gW2;
   float b2_g1, post_add_g1;    /* group 1 constants for UD_EPI_HEAD */
-  int tile_hint;               /* 0 = auto, 1 = force 128x128 tiles, 2 = force 256x256, 3 = force 192x256 (dense A only),
-                                  5 / 6 = 128x128 tiles: plain 2-stage kernel / 4-stage pipelined ring (6 is what auto picks when the
-                                  tile count is at most the CU count and K >= 512), 7 = 6 + the two-way K split below,
-                                  8 = row-balanced schedule of the 256-column kernel (dense A; auto picks it when the tile list
-                                  would leave the last round partly empty), 9 = 192x256 tiles with the 2-deep weight ring (dense
-                                  192-row launches otherwise fetch the weight operand two K-tiles ahead through a 3-deep LDS ring:
-                                  same bits, the weights of a layer are cold in every step),
-                                  10 = 192x256 tiles with the two-way K split of the large-tile list (splitk_ws_bytes below; refused -> 128x128 tiles) */
+  int tile_hint;               /* UD_HINT_* above: 0 = the cost model decides; the others force one schedule where it is eligible (tests, A/B tools) */
   /* optional scratch for the two-way K split of small problems (at most 128 tiles of 128x128, K >= 1024, dense A, F16 / F32
    * epilogues): two workgroups on different CUs each take half of K, the later one adds the other's fp32 partial tile (a + b is
    * order-independent, so results do not depend on timing) and runs the epilogue.  splitk_ws: 2 * tiles * 64 KB; splitk_cnt: one
@@ -149,10 +178,11 @@ typedef struct UdGemm {
 } UdGemm;
 
 int ud_gemm_f16(const UdGemm* desc, void* stream);
-/* kernel the call above would pick (profiling labels): 0/1/2 = 128-row tiles with BN 128/64/32, 3 = 192x256, 4 = 256x256, 5 = halo-tile conv,
- * 6 / 7 = 128x128 tiles, 4-stage pipelined ring without / with the two-way K split, 8 = row-balanced 256-column schedule;
- * + 16: folded-LayerNorm consumer instantiation, + 32: grouped problem run as one large-tile launch */
+/* the schedule the call above runs this descriptor on, UD_PICK_* above (code + flags); host code only, nothing is launched */
 int ud_gemm_pick(const UdGemm* desc);
+/* kernel class of that schedule as rocprofv3 prints it, e.g. "gemm256_kernel<3, 1, 0, false, false, false, true, false>" (profiling labels:
+ * profiles and bench lines join on it).  Writes at most cap bytes including the terminator; UD_ERR_BAD_ARG when the label does not fit. */
+int ud_gemm_kernel_name(const UdGemm* desc, char* buf, int cap);
 
 /* ---- LayerNorm (statistics only; the affine is folded into the consumer's weights at load time) ----
  * y(fp16)[orow, :] = (x[irow, :] - mean) * rsqrt(var + eps), biased variance (F.layer_norm).

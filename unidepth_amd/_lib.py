@@ -11,6 +11,14 @@ LIB_PATH = os.environ.get("UNIDEPTH_HIP_LIB", os.path.join(_HERE, "libunidepth_h
 UD_EPI_F16, UD_EPI_F32, UD_EPI_QKV, UD_EPI_D2S, UD_EPI_HEAD = 0, 1, 2, 3, 4
 UD_ACT_NONE, UD_ACT_GELU, UD_ACT_LRELU = 0, 1, 2
 UD_A_DENSE, UD_A_CONV3_ZERO, UD_A_CONV3_REFLECT, UD_A_CONV3_REFLECT_UP = 0, 1, 2, 3
+# UdGemm.tile_hint and the codes / flags of ud_gemm_pick (include/unidepth_hip.h)
+UD_HINT_AUTO, UD_HINT_TILE128, UD_HINT_LIST256, UD_HINT_LIST192 = 0, 1, 2, 3
+UD_HINT_PLAIN128, UD_HINT_RING, UD_HINT_RING_SPLITK, UD_HINT_BALANCED, UD_HINT_LIST192_W2, UD_HINT_LIST192_SPLITK = 5, 6, 7, 8, 9, 10
+UD_HINT_PINGPONG, UD_HINT_DUO_FIRST, UD_HINT_DUO_EQUAL, UD_HINT_DUO_SECOND = 11, 12, 13, 14
+UD_PICK_TILE128, UD_PICK_TILE128_BN64, UD_PICK_TILE128_BN32, UD_PICK_LIST192, UD_PICK_LIST256, UD_PICK_CONV_TILE = 0, 1, 2, 3, 4, 5
+UD_PICK_RING, UD_PICK_RING_SPLITK, UD_PICK_BALANCED, UD_PICK_LIST192_SPLITK, UD_PICK_PINGPONG, UD_PICK_DUO = 6, 7, 8, 10, 11, 12
+UD_PICK_SCHEDULE, UD_PICK_LN_CONSUMER, UD_PICK_GROUPED = 15, 16, 32
+UD_PICK_LARGE_TILE = (UD_PICK_LIST192, UD_PICK_LIST256, UD_PICK_BALANCED)     # the schedules that take a folded-LayerNorm consumer
 
 vp, fp, i32, i64, f32 = C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_float
 
@@ -138,6 +146,7 @@ def _load():
     sig = {
         "ud_gemm_f16": [P(UdGemm), vp],
         "ud_gemm_pick": [P(UdGemm)],
+        "ud_gemm_kernel_name": [P(UdGemm), C.c_char_p, i32],
         "ud_layernorm_f32_f16": [P(UdLayerNorm), vp],
         "ud_rccl_unique_id": [vp],
         "ud_rccl_init": [vp, i32, i32],

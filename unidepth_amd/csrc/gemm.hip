@@ -1549,184 +1549,6 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const UdGemm p) {
   }
 }
 
-// K split of the 192-row tile list (gemm256_kernel SPK): 2 * tiles workgroups; scratch per (tile, half) = 192 x 256 fp32
-constexpr size_t SPK_SLOT_BYTES = (size_t)192 * 256 * 4;
-template <int EPI, int AMODE>
-int launch256sk(const UdGemm& d, hipStream_t s) {
-  const int tiles = ((d.N + 255) >> 8) * ((d.M + 191) / 192);
-  const int lds = 2 * BigCfg<3>::STAGE + 64;
-  static bool attr_set[UD_MAX_DEVICES];
-  if (!ud_attr_once(attr_set)) {
-    if (hipFuncSetAttribute((const void*)gemm256_kernel<3, EPI, AMODE, false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      ud_set_error("ud_gemm_f16: cannot reserve the LDS ring of the large-tile kernel (K split)");
-      return UD_ERR_LAUNCH;
-    }
-  }
-  hipLaunchKernelGGL((gemm256_kernel<3, EPI, AMODE, false, false, false, false, true>), dim3(2 * tiles), dim3(512), lds, s, d);
-  UD_CHECK_LAUNCH("ud_gemm_f16 (large tile, K split) launch");
-  return UD_OK;
-}
-// eligibility of the K split of the large-tile list: a one-round list on at most half of the CUs, long K, plain fp16 / fp32 epilogues,
-// caller-provided scratch of 2 * tiles * SPK_SLOT_BYTES
-inline bool big_split_ok(const UdGemm& d) {
-#ifdef UD_AB_PREV
-  return false;
-#endif
-  if (d.amode != UD_A_DENSE && d.amode != UD_A_CONV3_ZERO) return false;
-  if (d.epi != UD_EPI_F16 && d.epi != UD_EPI_F32) return false;
-  if (d.groups > 1 || d.row_stats_in || d.row_stats_out || d.max_out || d.a_wrap || d.w_wrap || (d.K & 127) || d.K < 2048) return false;
-  const int tiles = ((d.N + 255) >> 8) * ((d.M + 191) / 192);
-  if (tiles > 128 || tiles < 32 || d.M < 1024 || d.N < 192) return false;
-  if (!d.splitk_ws || !d.splitk_cnt || (size_t)d.splitk_ws_bytes < 2 * (size_t)tiles * SPK_SLOT_BYTES) return false;
-  return true;
-}
-
-// W3 form of the 192-row tile list (3-deep weight ring, see the kernel): dense problems with at least two K-tiles.
-inline bool w3_enabled() { return true; }
-
-template <int MH, int EPI, int AMODE, bool LNC = false, bool GRP = false>
-int launch256(const UdGemm& d, hipStream_t s) {
-  constexpr int BM = BigCfg<MH>::BM;
-  const int tiles = ((d.N + 255) >> 8) * ((d.M + BM - 1) / BM);
-  if constexpr (MH == 3 && AMODE == UD_A_DENSE && !GRP) {
-    if (d.K >= 128 && d.tile_hint != 9 && w3_enabled()) {
-      const int lds3 = 2 * BigCfg<MH>::A_BYTES + 3 * 32768 + (LNC ? LNC_LDS : 0) + (EPI == UD_EPI_F32 ? 64 : 0);
-      static bool attr3_set[UD_MAX_DEVICES];
-      if (!ud_attr_once(attr3_set)) {
-        if (hipFuncSetAttribute((const void*)gemm256_kernel<MH, EPI, AMODE, false, LNC, GRP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds3) != hipSuccess) {
-          ud_set_error("ud_gemm_f16: cannot reserve the LDS rings of the large-tile kernel (3-deep weight ring)");
-          return UD_ERR_LAUNCH;
-        }
-      }
-      hipLaunchKernelGGL((gemm256_kernel<MH, EPI, AMODE, false, LNC, GRP, true>), dim3(tiles < 256 ? tiles : 256), dim3(512), lds3, s, d);
-      UD_CHECK_LAUNCH("ud_gemm_f16 (large tile, 3-deep weight ring) launch");
-      return UD_OK;
-    }
-  }
-  const int lds = 2 * BigCfg<MH>::STAGE + (LNC ? LNC_LDS : 0) + (EPI == UD_EPI_F32 ? 64 : 0);
-  static bool attr_set[UD_MAX_DEVICES];
-  if (!ud_attr_once(attr_set)) {
-    if (hipFuncSetAttribute((const void*)gemm256_kernel<MH, EPI, AMODE, false, LNC, GRP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      ud_set_error("ud_gemm_f16: cannot reserve the LDS ring of the large-tile kernel");
-      return UD_ERR_LAUNCH;
-    }
-  }
-  hipLaunchKernelGGL((gemm256_kernel<MH, EPI, AMODE, false, LNC, GRP>), dim3(tiles < 256 ? tiles : 256), dim3(512), lds, s, d);
-  UD_CHECK_LAUNCH("ud_gemm_f16 (large tile) launch");
-  return UD_OK;
-}
-
-// Row-balanced schedule (gemm256_kernel<4, EPI, DENSE, true>): worth it when the classic tile list leaves the last round partly empty.
-// Needs at least two 64-row units per workgroup (tile heights 128 / 192 / 256 only).
-inline int bal_cpc(const UdGemm& d) {
-  const int tiles_n = (d.N + 255) >> 8;
-  if (tiles_n > 128 || (d.N & 255)) return 0;
-  const int cpc = 256 / tiles_n;
-  const int U = (d.M + 63) >> 6;
-  return (U / cpc >= 2) ? cpc : 0;
-}
-// predicted time (us) of the balanced schedule, same units as pick_tiles: rows of the longest span at the 256-row tile's per-row
-// rate, plus the fixed cost and ~2.5 us of un-hidden prologue / epilogue per extra tile
-inline double bal_time(const UdGemm& d) {
-  const int cpc = bal_cpc(d);
-  if (!cpc) return 1e30;
-  const int U = (d.M + 63) >> 6;
-  const int un = (U + cpc - 1) / cpc;
-  const int k = (un + 3) >> 2;
-  return 8.0 + (un * (30.0 / 4.0) + (k - 1) * 2.5) * ((double)d.K / 1024.0);
-}
-
-template <int EPI, bool LNC = false, int AMODE = UD_A_DENSE>
-int launch256bal(const UdGemm& d, hipStream_t s) {
-  const int tiles_n = (d.N + 255) >> 8;
-  const int cpc = bal_cpc(d);
-  const int lds = 2 * BigCfg<4>::STAGE + (LNC ? LNC_LDS : 0);
-  static bool attr_set[UD_MAX_DEVICES];
-  if (!ud_attr_once(attr_set)) {
-    if (hipFuncSetAttribute((const void*)gemm256_kernel<4, EPI, AMODE, true, LNC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      ud_set_error("ud_gemm_f16: cannot reserve the LDS ring of the large-tile kernel");
-      return UD_ERR_LAUNCH;
-    }
-  }
-  hipLaunchKernelGGL((gemm256_kernel<4, EPI, AMODE, true, LNC>), dim3(cpc * tiles_n), dim3(512), lds, s, d);
-  UD_CHECK_LAUNCH("ud_gemm_f16 (large tile, row-balanced) launch");
-  return UD_OK;
-}
-
-// Tile-shape choice for dense GEMMs.  Cost model fitted on MI355X (tools/bench_gemm*.py): per-launch fixed cost + rounds x
-// K-loop time per round.  The large-tile kernel (one workgroup per CU) loses to wave quantisation when the tile count is
-// small or just above a multiple of 256 CUs; the 128x128 kernel runs two workgroups per CU, so its rounds quantise in halves.
-// Returns 0 (128x128), 3 (192x256) or 4 (256x256).
-inline int pick_tiles(const UdGemm& d) {
-  if (d.amode == UD_A_CONV3_REFLECT || d.groups > 1 || d.M < 1024 || d.N < 192 || (d.K & 63)) return 0;
-  if (d.amode == UD_A_CONV3_ZERO && d.epi != UD_EPI_F16 && d.epi != UD_EPI_F32) return 0;
-  {  // the large-tile loader addresses its operands with 32-bit byte offsets inside 2 GB buffer descriptors
-    const double a_bytes = d.amode == UD_A_DENSE ? 2.0 * d.M * d.lda : 2.0 * ((double)(d.M / d.rows_img) + 1.0) * (double)d.img_stride;
-    if (a_bytes >= 2147483648.0 || 2.0 * d.N * d.ldw >= 2147483648.0) return 0;
-  }
-  if (d.epi == UD_EPI_QKV && (d.vsplit & 255)) return 0;
-  if (d.tile_hint == 1 || (d.tile_hint >= 5 && d.tile_hint != 8 && d.tile_hint != 9 && d.tile_hint != 10 && (d.tile_hint < 11 || d.tile_hint > 14))) return 0;
-  if (d.tile_hint >= 11 && d.tile_hint <= 14) return 3;         // ping-pong / duo forms refused (gemm_pp.hip): the 192-row list
-  if (d.tile_hint == 2) return 4;
-  if (d.tile_hint == 10) return big_split_ok(d) ? 10 : 0;       // 10: 192-row tile list with the two-way K split (when eligible)
-  if (d.tile_hint == 3 || d.tile_hint == 9) return 3;      // 9: 192-row tile list with the 2-deep weight ring (A/B and tests of the 3-deep form)
-  const bool bal_ok = (d.amode == UD_A_DENSE || (d.amode == UD_A_CONV3_ZERO && d.epi != UD_EPI_QKV)) &&
-                      (d.epi == UD_EPI_F16 || d.epi == UD_EPI_F32 || d.epi == UD_EPI_QKV) && bal_cpc(d) > 0;
-  if (d.tile_hint == 8 && bal_ok) return 8;
-  const double kk = (double)d.K / 1024.0;
-  const double tn = (double)((d.N + 255) / 256);
-  const double t256 = 8.0 + ceil(tn * ((d.M + 255) / 256) / 256.0) * 30.0 * kk;
-  const double t192 = 8.0 + ceil(tn * ((d.M + 191) / 192) / 256.0) * 23.5 * kk;
-  // a span of one tile per workgroup cannot finish earlier than the tile list does (proj / fc2 at bs = 8: 192 rows either way, and the
-  // MH = 4 instantiation measured 4 % slower there): the balanced schedule competes only when spans hold two or more tiles
-  const double tbal = (bal_ok && ((d.M + 63) / 64 + bal_cpc(d) - 1) / bal_cpc(d) > 4) ? bal_time(d) : 1e30;
-  const double small_tiles = (double)((d.N + 127) / 128) * ((d.M + 127) / 128);
-  const double t_small = 6.0 + ceil(small_tiles / 256.0) * 0.5 * 21.5 * kk;
-  double t_big = t256 <= t192 ? t256 : t192;
-  int which = t256 <= t192 ? 4 : 3;
-  if (tbal < 0.985 * t_big) { t_big = tbal; which = 8; }      // measured: fc1 94.5 vs 98.5 us (model 95.5 / 98), qkv 82 vs 74.5 (80.5 / 78.5)
-  if (big_split_ok(d)) {                                       // half the K loop on twice the workgroups + ~6 us for the exchange of the partial tiles
-    const double tsplit = 8.0 + 0.5 * 23.5 * kk + 6.0;
-    if (tsplit < t_big && tsplit < 0.93 * t_small) return 10;
-  }
-  if (t_big >= 0.93 * t_small) return 0;
-  return which;
-}
-
-// tiles one workgroup of the large-tile kernel walks for this problem (the folded-LayerNorm consumer keeps one statistics table per tile)
-inline int big_tiles_per_wg(const UdGemm& d, int which) {
-  if (which == 8) {
-    const int cpc = bal_cpc(d);
-    const int U = (d.M + 63) >> 6;
-    return (((U + cpc - 1) / cpc) + 3) >> 2;
-  }
-  if (which == 10) return 1;
-  const int bm = which == 3 ? 192 : 256;
-  const int tiles = ((d.N + 255) >> 8) * ((d.M + bm - 1) / bm);
-  return (tiles + 255) / 256;
-}
-
-template <int EPI, int AMODE = UD_A_DENSE>
-int launch_big(const UdGemm& d, hipStream_t s, int which) {
-  if constexpr (AMODE == UD_A_DENSE && (EPI == UD_EPI_F16 || EPI == UD_EPI_QKV)) {
-    if (d.row_stats_in) {                 // consumer of a folded LayerNorm: separate instantiations (statistics table in LDS)
-      if (which == 8) return launch256bal<EPI, true>(d, s);
-      return which == 3 ? launch256<3, EPI, AMODE, true>(d, s) : launch256<4, EPI, AMODE, true>(d, s);
-    }
-  }
-  if constexpr (AMODE == UD_A_DENSE && (EPI == UD_EPI_F16 || EPI == UD_EPI_F32 || EPI == UD_EPI_QKV)) {
-    if (which == 8 && !d.row_stats_final) return launch256bal<EPI>(d, s);
-  }
-  if constexpr (AMODE == UD_A_CONV3_ZERO && (EPI == UD_EPI_F16 || EPI == UD_EPI_F32)) {
-    if (which == 8 && !d.row_stats_final) return launch256bal<EPI, false, UD_A_CONV3_ZERO>(d, s);
-  }
-  if constexpr (EPI == UD_EPI_F16 || EPI == UD_EPI_F32) {
-    if (which == 10) return launch256sk<EPI, AMODE>(d, s);
-  }
-  if (which == 8 || which == 10) which = 3;               // in-kernel statistics reduction: tickets are per row tile of ONE height (tile list only)
-  return which == 3 ? launch256<3, EPI, AMODE>(d, s) : launch256<4, EPI, AMODE>(d, s);
-}
-
 // ================================================================================================================
 // Halo-tile 3x3 convolution for narrow outputs (N <= 64: the two head convolutions, decoder.py:199-226).
 // The implicit-GEMM kernels above re-gather every input pixel once per tap (9x) through L2 -> LDS; with N <= 64 there is so
@@ -2103,101 +1925,145 @@ __global__ __launch_bounds__(256, 2) void conv_head_regw_kernel(const UdGemm p, 
   }
 }
 
+// ================================================================================================================
+// Host side.  route() decides ONCE which schedule and which instantiation a descriptor runs on; ud_gemm_f16 (the launch),
+// ud_gemm_pick (the integer code) and ud_gemm_kernel_name (the profiling label) only read that Route.
+// ================================================================================================================
+constexpr size_t SPK_SLOT_BYTES = (size_t)192 * 256 * 4;   // K split of the 192-row tile list: scratch per (tile, half) = 192 x 256 fp32
 constexpr int UPS_PATCH = 13;                  // source patch side of the fused up-sampling loader (halo of 18 at a scale <= 0.6, + 2)
-template <int NT, int EPI, bool REFLECT, bool UPS = false>
-int launch_conv_tile(const UdGemm& d, hipStream_t s) {
-  const int lds = HALO_BYTES + 2 * NT * 16 * 128 + (UPS ? (UPS_PATCH * UPS_PATCH * 128 + 1023) / 1024 * 1024 : 0);
-  if (UPS) {
-    static bool attr_set[UD_MAX_DEVICES];
-    if (!ud_attr_once(attr_set)) (void)hipFuncSetAttribute((const void*)conv_tile_kernel<NT, EPI, REFLECT, UPS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  }
-  const int B = d.M / d.rows_img;
-  dim3 grid(((d.Wimg + 15) >> 4) * ((d.Himg + 15) >> 4), B, d.groups > 0 ? d.groups : 1);
-  hipLaunchKernelGGL((conv_tile_kernel<NT, EPI, REFLECT, UPS>), grid, dim3(256), lds, s, d);
-  UD_CHECK_LAUNCH("ud_gemm_f16 (halo-tile conv) launch");
-  return UD_OK;
+
+enum Sched {
+  S_TILE128,       // gemm_kernel, plain 2-stage ring: 128-row tiles of BN 128 / 64 / 32 columns
+  S_RING,          // gemm_kernel<Cfg<128, 64, 64>>, 4-stage pipelined ring, optionally with the two-way K split across CUs
+  S_LIST,          // gemm256_kernel walking a list of 192- or 256-row tiles
+  S_BALANCED,      // gemm256_kernel, row-balanced spans
+  S_LIST_SPLITK,   // gemm256_kernel, 192-row tile list with the two-way K split
+  S_PINGPONG,      // gemm_pp_f32_kernel<3, 8> (gemm_pp.hip)
+  S_DUO,           // gemm_pp_f32_kernel<3, 4>: two workgroups per CU (gemm_pp.hip)
+  S_CONV_TILE,     // conv_tile_kernel
+  S_HEAD_REGW      // conv_head_regw_kernel
+};
+
+struct Route {
+  Sched sched;
+  bool large;       // the tile-shape model gives the problem to the large-tile kernels (what row_stats_in / row_stats_out need)
+  int bn;           // S_TILE128: tile width 128 / 64 / 32
+  bool splitk;      // S_RING: two-way K split across CUs
+  int mh;           // S_LIST: tile height in 64-row units, 3 / 4
+  bool lnc;         // S_LIST, S_BALANCED: consumer of a folded LayerNorm (statistics table in LDS)
+  bool grp;         // S_LIST: a grouped problem as ONE tile list; `merged` is the descriptor that is launched
+  bool w3;          // S_LIST: 3-deep weight ring
+  int nt;           // S_CONV_TILE: output channels / 16
+  int prio;         // S_DUO: priority mode of the kernel
+  UdGemm merged;
+};
+
+// eligibility of the K split of the large-tile list: a one-round list on at most half of the CUs, long K, plain fp16 / fp32 epilogues,
+// caller-provided scratch of 2 * tiles * SPK_SLOT_BYTES
+inline bool big_split_ok(const UdGemm& d) {
+  if (d.amode != UD_A_DENSE && d.amode != UD_A_CONV3_ZERO) return false;
+  if (d.epi != UD_EPI_F16 && d.epi != UD_EPI_F32) return false;
+  if (d.groups > 1 || d.row_stats_in || d.row_stats_out || d.max_out || d.a_wrap || d.w_wrap || (d.K & 127) || d.K < 2048) return false;
+  const int tiles = ((d.N + 255) >> 8) * ((d.M + 191) / 192);
+  if (tiles > 128 || tiles < 32 || d.M < 1024 || d.N < 192) return false;
+  if (!d.splitk_ws || !d.splitk_cnt || (size_t)d.splitk_ws_bytes < 2 * (size_t)tiles * SPK_SLOT_BYTES) return false;
+  return true;
 }
 
-inline bool head_regw_enabled() { return true; }
+// Row-balanced schedule (gemm256_kernel<4, EPI, AMODE, true>): worth it when the classic tile list leaves the last round partly empty.
+// Needs at least two 64-row units per workgroup (tile heights 128 / 192 / 256 only).  Returns the workgroups per tile column, 0 = not eligible.
+inline int bal_cpc(const UdGemm& d) {
+  const int tiles_n = (d.N + 255) >> 8;
+  if (tiles_n > 128 || (d.N & 255)) return 0;
+  const int cpc = 256 / tiles_n;
+  const int U = (d.M + 63) >> 6;
+  return (U / cpc >= 2) ? cpc : 0;
+}
+// predicted time (us) of the balanced schedule, same units as pick_tiles: rows of the longest span at the 256-row tile's per-row
+// rate, plus the fixed cost and ~2.5 us of un-hidden prologue / epilogue per extra tile
+inline double bal_time(const UdGemm& d, int cpc) {
+  const int U = (d.M + 63) >> 6;
+  const int un = (U + cpc - 1) / cpc;
+  const int k = (un + 3) >> 2;
+  return 8.0 + (un * (30.0 / 4.0) + (k - 1) * 2.5) * ((double)d.K / 1024.0);
+}
 
-// eligibility: dense images (rows_img == H*W), N in {32, 64}, Cin multiple of 64, weights laid out [N][tap*Cin + ci]
+// Tile-shape choice for dense GEMMs.  Cost model fitted on MI355X (tools/bench_gemm*.py): per-launch fixed cost + rounds x
+// K-loop time per round.  The large-tile kernel (one workgroup per CU) loses to wave quantisation when the tile count is
+// small or just above a multiple of 256 CUs; the 128x128 kernel runs two workgroups per CU, so its rounds quantise in halves.
+// Returns UD_PICK_TILE128 (the 128-row kernels), UD_PICK_LIST192, UD_PICK_LIST256, UD_PICK_BALANCED or UD_PICK_LIST192_SPLITK.
+inline int pick_tiles(const UdGemm& d) {
+  if (d.amode == UD_A_CONV3_REFLECT || d.groups > 1 || d.M < 1024 || d.N < 192 || (d.K & 63)) return UD_PICK_TILE128;
+  if (d.amode != UD_A_DENSE && d.rows_img <= 0) return UD_PICK_TILE128;      // (no image geometry: nothing to divide by below)
+  if (d.amode == UD_A_CONV3_ZERO && d.epi != UD_EPI_F16 && d.epi != UD_EPI_F32) return UD_PICK_TILE128;
+  {  // the large-tile loader addresses its operands with 32-bit byte offsets inside 2 GB buffer descriptors
+    const double a_bytes = d.amode == UD_A_DENSE ? 2.0 * d.M * d.lda : 2.0 * ((double)(d.M / d.rows_img) + 1.0) * (double)d.img_stride;
+    if (a_bytes >= 2147483648.0 || 2.0 * d.N * d.ldw >= 2147483648.0) return UD_PICK_TILE128;
+  }
+  if (d.epi == UD_EPI_QKV && (d.vsplit & 255)) return UD_PICK_TILE128;
+  const int cpc = bal_cpc(d);
+  const bool bal_ok = (d.amode == UD_A_DENSE || (d.amode == UD_A_CONV3_ZERO && d.epi != UD_EPI_QKV)) &&
+                      (d.epi == UD_EPI_F16 || d.epi == UD_EPI_F32 || d.epi == UD_EPI_QKV) && cpc > 0;
+  switch (d.tile_hint) {
+    case UD_HINT_TILE128: case UD_HINT_PLAIN128: case UD_HINT_RING: case UD_HINT_RING_SPLITK: return UD_PICK_TILE128;
+    case UD_HINT_LIST256: return UD_PICK_LIST256;
+    case UD_HINT_LIST192: case UD_HINT_LIST192_W2: return UD_PICK_LIST192;      // W2: the 2-deep weight ring (A/B and tests of the 3-deep form)
+    case UD_HINT_LIST192_SPLITK: return big_split_ok(d) ? UD_PICK_LIST192_SPLITK : UD_PICK_TILE128;
+    case UD_HINT_PINGPONG: case UD_HINT_DUO_FIRST: case UD_HINT_DUO_EQUAL: case UD_HINT_DUO_SECOND:
+      return UD_PICK_LIST192;                                                    // ping-pong / duo forms refused (gemm_pp.hip): the 192-row list
+    case UD_HINT_BALANCED: if (bal_ok) return UD_PICK_BALANCED; break;           // not eligible: the cost model
+    default: if (d.tile_hint > UD_HINT_DUO_SECOND) return UD_PICK_TILE128; break;   // unassigned values above the last hint; the others: the cost model
+  }
+  const double kk = (double)d.K / 1024.0;
+  const double tn = (double)((d.N + 255) / 256);
+  const double t256 = 8.0 + ceil(tn * ((d.M + 255) / 256) / 256.0) * 30.0 * kk;
+  const double t192 = 8.0 + ceil(tn * ((d.M + 191) / 192) / 256.0) * 23.5 * kk;
+  // a span of one tile per workgroup cannot finish earlier than the tile list does (proj / fc2 at bs = 8: 192 rows either way, and the
+  // MH = 4 instantiation measured 4 % slower there): the balanced schedule competes only when spans hold two or more tiles
+  const double tbal = (bal_ok && ((d.M + 63) / 64 + cpc - 1) / cpc > 4) ? bal_time(d, cpc) : 1e30;
+  const double small_tiles = (double)((d.N + 127) / 128) * ((d.M + 127) / 128);
+  const double t_small = 6.0 + ceil(small_tiles / 256.0) * 0.5 * 21.5 * kk;
+  double t_big = t256 <= t192 ? t256 : t192;
+  int which = t256 <= t192 ? UD_PICK_LIST256 : UD_PICK_LIST192;
+  if (tbal < 0.985 * t_big) { t_big = tbal; which = UD_PICK_BALANCED; }      // measured: fc1 94.5 vs 98.5 us (model 95.5 / 98), qkv 82 vs 74.5 (80.5 / 78.5)
+  if (big_split_ok(d)) {                                       // half the K loop on twice the workgroups + ~6 us for the exchange of the partial tiles
+    const double tsplit = 8.0 + 0.5 * 23.5 * kk + 6.0;
+    if (tsplit < t_big && tsplit < 0.93 * t_small) return UD_PICK_LIST192_SPLITK;
+  }
+  if (t_big >= 0.93 * t_small) return UD_PICK_TILE128;
+  return which;
+}
+
+// halo-tile convolution, eligibility: dense images (rows_img == H*W), N in {32, 64}, Cin multiple of 64, weights laid out [N][tap*Cin + ci]
 inline bool conv_tile_ok(const UdGemm& d) {
-  return d.amode != UD_A_DENSE && d.a_wrap == 0 && (d.N == 32 || d.N == 64) && (d.Cin & 63) == 0 && d.rows_img == d.Himg * d.Wimg &&
-         d.M % d.rows_img == 0 && d.bias != nullptr && d.tile_hint != 1 && d.Himg >= 2 && d.Wimg >= 2 &&
+  return d.amode != UD_A_DENSE && d.a_wrap == 0 && (d.N == 32 || d.N == 64) && (d.Cin & 63) == 0 && d.Himg >= 2 && d.Wimg >= 2 &&
+         d.rows_img == d.Himg * d.Wimg && d.M % d.rows_img == 0 && d.bias != nullptr && d.tile_hint != UD_HINT_TILE128 &&
          (d.epi == UD_EPI_HEAD || (d.epi == UD_EPI_F16 && d.act != UD_ACT_GELU && d.rows_in == 0 && d.add == nullptr && (d.ldc & 3) == 0));
 }
 
 // Variant of the dense 128 x 128 kernel (N > 64; F16 / F32 / QKV epilogues): 0 = plain 2-stage ring, 1 = 4-stage pipelined ring,
 // 2 = ring + two-way K split across CUs.  With at most one workgroup per CU anyway (tile count <= CU count: small batches) the
 // plain kernel, tuned for two co-resident workgroups hiding each other's stalls, leaves the CU idle through every DMA / LDS round
-// trip.  tile_hint 5 keeps the plain kernel, 6 forces the ring without the split, 7 the split (when the scratch is there).
-inline int ring_variant(const UdGemm& d) {
+// trip.  UD_HINT_PLAIN128 keeps the plain kernel, UD_HINT_RING forces the ring without the split, UD_HINT_RING_SPLITK the split (when
+// the scratch is there); every hint above UD_HINT_RING forces the ring like it.  dbg: bisect switches of tools builds, bit 4 = no ring,
+// bit 5 = no K split.
+inline int ring_variant(const UdGemm& d, int dbg) {
   const int tiles = ((d.N + 127) / 128) * ((d.M + 127) / 128);
   const int nkt = d.K >> 6;
   if (d.amode != UD_A_DENSE || d.N <= 64 || (d.epi != UD_EPI_F16 && d.epi != UD_EPI_F32 && d.epi != UD_EPI_QKV)) return 0;
-  if (!(d.groups <= 1 && nkt >= 4 && d.tile_hint != 5 && ((tiles <= 256 && nkt >= 8) || d.tile_hint >= 6) && !(ud_debug_flags_host() & 16))) return 0;
-  if (d.epi != UD_EPI_QKV && d.splitk_ws && d.splitk_cnt && tiles <= 128 && (nkt & 1) == 0 && (nkt >= 16 || (d.tile_hint == 7 && nkt >= 8)) &&
-      d.tile_hint != 6 && !(ud_debug_flags_host() & 32))
+  if (!(d.groups <= 1 && nkt >= 4 && d.tile_hint != UD_HINT_PLAIN128 && ((tiles <= 256 && nkt >= 8) || d.tile_hint >= UD_HINT_RING) && !(dbg & 16))) return 0;
+  if (d.epi != UD_EPI_QKV && d.splitk_ws && d.splitk_cnt && tiles <= 128 && (nkt & 1) == 0 && (nkt >= 16 || (d.tile_hint == UD_HINT_RING_SPLITK && nkt >= 8)) &&
+      d.tile_hint != UD_HINT_RING && !(dbg & 32))
     return 2;
   return 1;
-}
-
-template <class C, int EPI, int AMODE>
-int launch(const UdGemm& d, hipStream_t s) {
-  const int tiles_n = (d.N + C::BN - 1) / C::BN;
-  const int tiles_m = (d.M + C::BM - 1) / C::BM;
-  if constexpr (C::BN == 128 && AMODE == UD_A_DENSE && (EPI == UD_EPI_F16 || EPI == UD_EPI_F32 || EPI == UD_EPI_QKV)) {
-    const int variant = ring_variant(d);
-    if (variant) {
-      const int lds4 = 4 * C::STAGE_BYTES;
-      if constexpr (EPI == UD_EPI_F16 || EPI == UD_EPI_F32) {
-        if (variant == 2) {              // two-way K split across CUs: twice the workgroups, i.e. twice the DMA bytes in flight
-          static bool attrs_set[UD_MAX_DEVICES];
-          if (!ud_attr_once(attrs_set)) {
-            if (hipFuncSetAttribute((const void*)gemm_kernel<C, EPI, AMODE, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4) != hipSuccess) {
-              ud_set_error("ud_gemm_f16: cannot reserve the 4-stage LDS ring");
-              return UD_ERR_LAUNCH;
-            }
-          }
-          hipLaunchKernelGGL((gemm_kernel<C, EPI, AMODE, 4, true>), dim3(2 * tiles_m * tiles_n), dim3(256), lds4, s, d);
-          UD_CHECK_LAUNCH("ud_gemm_f16 (4-stage ring, K split) launch");
-          return UD_OK;
-        }
-      }
-      static bool attr4_set[UD_MAX_DEVICES];
-      if (!ud_attr_once(attr4_set)) {
-        if (hipFuncSetAttribute((const void*)gemm_kernel<C, EPI, AMODE, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4) != hipSuccess) {
-          ud_set_error("ud_gemm_f16: cannot reserve the 4-stage LDS ring");
-          return UD_ERR_LAUNCH;
-        }
-      }
-      hipLaunchKernelGGL((gemm_kernel<C, EPI, AMODE, 4>), dim3(tiles_m * tiles_n), dim3(256), lds4, s, d);
-      UD_CHECK_LAUNCH("ud_gemm_f16 (4-stage ring) launch");
-      return UD_OK;
-    }
-  }
-  const int lds = 2 * C::STAGE_BYTES;
-  static bool attr_set[UD_MAX_DEVICES];
-  if (!ud_attr_once(attr_set)) (void)hipFuncSetAttribute((const void*)gemm_kernel<C, EPI, AMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  dim3 grid(tiles_m * tiles_n, 1, d.groups > 0 ? d.groups : 1);
-  hipLaunchKernelGGL((gemm_kernel<C, EPI, AMODE>), grid, dim3(256), lds, s, d);
-  UD_CHECK_LAUNCH("ud_gemm_f16 launch");
-  return UD_OK;
-}
-
-template <int EPI, int AMODE>
-int dispatch_bn(const UdGemm& d, hipStream_t s) {
-  if (d.N > 64) return launch<Cfg<128, 64, 64>, EPI, AMODE>(d, s);
-  if (d.N > 32) return launch<Cfg<64, 64, 32>, EPI, AMODE>(d, s);
-  return launch<Cfg<32, 32, 32>, EPI, AMODE>(d, s);
 }
 
 // A grouped dense problem as ONE launch of the 256 x 256 kernel (gemm256_kernel GRP): groups stacked along M (A rows shared or stacked,
 // outputs stacked), rows per group a multiple of the tile height.  Returns true and the merged descriptor when that form applies and
 // the tile-shape model prefers the large kernel for the merged problem.
 inline bool grouped_as_big(const UdGemm& d, UdGemm& m) {
-  if (d.groups <= 1 || d.amode != UD_A_DENSE || (d.M & 255) || d.tile_hint == 1 || d.a_wrap || d.w_wrap || d.row_stats_in || d.row_stats_out || d.max_out ||
-      d.rows_in || d.add)
+  if (d.groups <= 1 || d.amode != UD_A_DENSE || (d.M & 255) || d.tile_hint == UD_HINT_TILE128 || d.a_wrap || d.w_wrap || d.row_stats_in || d.row_stats_out ||
+      d.max_out || d.rows_in || d.add)
     return false;
   // fp16 epilogues only: the fp32 (accumulate) epilogues of the x4 launches are traffic-bound (fp32 read + write of the stream) and ran
   // SLOWER as 344 large tiles with the residual preload exposed per tile (dh.out 68 -> 80 us, dh.fc2 147 -> 164 us, adapters 89 -> 86)
@@ -2205,10 +2071,7 @@ inline bool grouped_as_big(const UdGemm& d, UdGemm& m) {
   // profiles/r03_ops_per_launch.tsv against the r3c5 run)
   // round 6 (tools/r6_dec_ab.py, same process, interleaved): the non-accumulating fp32 launch (the four input adapters, K = 1024) 80 -> 70 us as one
   // large-tile list; the accumulating ones unchanged or slower again (dh.out 58 / 58 us, dh.fc2 150 / 158 us)
-#ifdef UD_AB_PREV
-  if (d.epi != UD_EPI_F16 && d.epi != UD_EPI_QKV) return false;
-#endif
-  if (d.epi != UD_EPI_F16 && d.epi != UD_EPI_QKV && !(d.epi == UD_EPI_F32 && (d.tile_hint == 2 || (d.accumulate == 0 && d.K >= 1024)))) return false;
+  if (d.epi != UD_EPI_F16 && d.epi != UD_EPI_QKV && !(d.epi == UD_EPI_F32 && (d.tile_hint == UD_HINT_LIST256 || (d.accumulate == 0 && d.K >= 1024)))) return false;
   if (!(d.gA == 0 || d.gA == (long long)d.M * d.lda) || d.gOut != (long long)d.M * d.ldc) return false;
   if (d.bias && d.gBias < 0) return false;
   if (d.out2) {
@@ -2223,42 +2086,260 @@ inline bool grouped_as_big(const UdGemm& d, UdGemm& m) {
   m.M = d.M * d.groups;
   m.groups = 1;
   if (2.0 * (double)d.groups * d.N * d.ldw >= 2147483648.0 || 2.0 * (double)m.M * d.lda >= 2147483648.0) return false;
-  m.tile_hint = 0;
+  m.tile_hint = UD_HINT_AUTO;
   const int bt = pick_tiles(m);
-  return bt == 4 || bt == 3 || bt == 8;         // the merged problem is large enough for the large-tile kernel (it then runs 256-row tiles)
+  // the merged problem is large enough for the large-tile kernel (it then runs 256-row tiles)
+  return bt == UD_PICK_LIST256 || bt == UD_PICK_LIST192 || bt == UD_PICK_BALANCED;
 }
 
 }  // namespace
 
-// ping-pong form of the 192-row tile for the fp32 residual-accumulate class (gemm_pp.hip): one-round tile lists (tile_hint 11 forces it
-// where eligible, 0 picks it when the cost model would take the 192-row list and the list fits one round)
+// ping-pong and two-workgroups-per-CU forms of the 192-row tile for the fp32 residual-accumulate class (gemm_pp.hip)
 bool ud_gemm_pp_ok(const UdGemm& d);
 int ud_gemm_pp_launch(const UdGemm& d, hipStream_t s);
 bool ud_gemm_duo_ok(const UdGemm& d);
 int ud_gemm_duo_launch(const UdGemm& d, hipStream_t s, int prio_mode);
+
 namespace {
-inline bool pp_pick(const UdGemm& d) {
-#ifdef UD_AB_PREV      // A/B builds only (tools/r6/sessions.sh: ab/libprev.so = this tree with the round-6 schedules switched off, same ABI)
-  return false;
-#endif
-  if (!ud_gemm_pp_ok(d)) return false;
-  if (d.tile_hint == 11) return true;
-  if (d.tile_hint != 0) return false;
-  const int tiles = (d.N >> 8) * ((d.M + 191) / 192);
-  return tiles <= 256 && tiles >= 128 && pick_tiles(d) == 3;
+
+// The one decision.  Pure host code: no HIP call, the descriptor's pointers are only tested against null.
+Route route(const UdGemm& d) {
+  Route r{};
+  const bool f16 = d.epi == UD_EPI_F16, f32 = d.epi == UD_EPI_F32, qkv = d.epi == UD_EPI_QKV, head = d.epi == UD_EPI_HEAD;
+  const int bt = head ? UD_PICK_TILE128 : pick_tiles(d);
+  r.large = bt != UD_PICK_TILE128;
+  if ((f16 || f32 || qkv) && grouped_as_big(d, r.merged)) {
+    r.sched = S_LIST;
+    r.mh = 4;
+    r.grp = true;
+    return r;
+  }
+  if ((head || f16) && conv_tile_ok(d)) {
+    // 64 input channels under the fused up-sampling: weights in registers, persistent workgroups
+    r.sched = head && d.amode == UD_A_CONV3_REFLECT_UP && d.Cin == 64 ? S_HEAD_REGW : S_CONV_TILE;
+    r.nt = d.N / 16;
+    return r;
+  }
+  if (f32 && d.tile_hint >= UD_HINT_DUO_FIRST && d.tile_hint <= UD_HINT_DUO_SECOND && ud_gemm_duo_ok(d)) {   // measured slower: by hint only
+    r.sched = S_DUO;
+    r.prio = d.tile_hint == UD_HINT_DUO_FIRST ? 1 : d.tile_hint == UD_HINT_DUO_EQUAL ? 0 : 2;
+    return r;
+  }
+  if (f32 && (d.tile_hint == UD_HINT_PINGPONG || d.tile_hint == UD_HINT_AUTO) && ud_gemm_pp_ok(d)) {
+    // one-round tile lists: forced where eligible, picked when the cost model would take the 192-row list and the list fits one round
+    const int tiles = (d.N >> 8) * ((d.M + 191) / 192);
+    if (d.tile_hint == UD_HINT_PINGPONG || (tiles <= 256 && tiles >= 128 && bt == UD_PICK_LIST192)) {
+      r.sched = S_PINGPONG;
+      return r;
+    }
+  }
+  if (r.large) {
+    r.lnc = d.row_stats_in != nullptr;          // consumer of a folded LayerNorm: separate instantiations
+    if (bt == UD_PICK_LIST192_SPLITK) {
+      r.sched = S_LIST_SPLITK;
+    } else if (bt == UD_PICK_BALANCED && !d.row_stats_final) {
+      r.sched = S_BALANCED;
+    } else {      // the tile list; a balanced pick with row_stats_final too (in-kernel statistics reduction: tickets are per row tile of ONE height, 192 rows)
+      r.sched = S_LIST;
+      r.mh = bt == UD_PICK_LIST256 ? 4 : 3;
+      // W3 form of the 192-row tile list (3-deep weight ring, see the kernel): dense problems with at least two K-tiles
+      r.w3 = r.mh == 3 && d.amode == UD_A_DENSE && d.K >= 128 && d.tile_hint != UD_HINT_LIST192_W2;
+    }
+    return r;
+  }
+  const int ring = d.N > 64 && d.epi != UD_EPI_D2S ? ring_variant(d, ud_debug_flags_host()) : 0;
+  if (ring) {
+    r.sched = S_RING;
+    r.splitk = ring == 2;
+    return r;
+  }
+  r.sched = S_TILE128;
+  r.bn = d.N > 64 ? 128 : d.N > 32 ? 64 : 32;
+  return r;
 }
+
+int pick_code(const Route& r) {
+  switch (r.sched) {
+    case S_TILE128: return r.bn == 128 ? UD_PICK_TILE128 : r.bn == 64 ? UD_PICK_TILE128_BN64 : UD_PICK_TILE128_BN32;
+    case S_RING: return r.splitk ? UD_PICK_RING_SPLITK : UD_PICK_RING;
+    case S_LIST: return (r.mh == 3 ? UD_PICK_LIST192 : UD_PICK_LIST256) + (r.lnc ? UD_PICK_LN_CONSUMER : 0) + (r.grp ? UD_PICK_GROUPED : 0);
+    case S_BALANCED: return UD_PICK_BALANCED + (r.lnc ? UD_PICK_LN_CONSUMER : 0);
+    case S_LIST_SPLITK: return UD_PICK_LIST192_SPLITK;
+    case S_PINGPONG: return UD_PICK_PINGPONG;
+    case S_DUO: return UD_PICK_DUO;
+    case S_CONV_TILE: case S_HEAD_REGW: return UD_PICK_CONV_TILE;
+  }
+  return -1;
+}
+
+// the instantiation as rocprofv3 prints it: the template arguments below are the ones launch_route() passes
+int kernel_name(const Route& r, const UdGemm& d, char* buf, int cap) {
+  const auto b = [](bool v) { return v ? "true" : "false"; };
+  int n = -1;
+  switch (r.sched) {
+    case S_TILE128:
+      n = snprintf(buf, cap, "gemm_kernel<Cfg<%s>, %d, %d, 2, false>", r.bn == 128 ? "128, 64, 64" : r.bn == 64 ? "64, 64, 32" : "32, 32, 32", d.epi, d.amode);
+      break;
+    case S_RING: n = snprintf(buf, cap, "gemm_kernel<Cfg<128, 64, 64>, %d, %d, 4, %s>", d.epi, d.amode, b(r.splitk)); break;
+    case S_LIST: n = snprintf(buf, cap, "gemm256_kernel<%d, %d, %d, false, %s, %s, %s, false>", r.mh, d.epi, d.amode, b(r.lnc), b(r.grp), b(r.w3)); break;
+    case S_BALANCED: n = snprintf(buf, cap, "gemm256_kernel<4, %d, %d, true, %s, false, false, false>", d.epi, d.amode, b(r.lnc)); break;
+    case S_LIST_SPLITK: n = snprintf(buf, cap, "gemm256_kernel<3, %d, %d, false, false, false, false, true>", d.epi, d.amode); break;
+    case S_PINGPONG: n = snprintf(buf, cap, "gemm_pp_f32_kernel<3, 8>"); break;
+    case S_DUO: n = snprintf(buf, cap, "gemm_pp_f32_kernel<3, 4>"); break;
+    case S_CONV_TILE:
+      n = snprintf(buf, cap, "conv_tile_kernel<%d, %d, %s, %s>", r.nt, d.epi, b(d.amode >= UD_A_CONV3_REFLECT), b(d.amode == UD_A_CONV3_REFLECT_UP));
+      break;
+    case S_HEAD_REGW: n = snprintf(buf, cap, "conv_head_regw_kernel"); break;
+  }
+  return n >= 0 && n < cap ? UD_OK : UD_ERR_BAD_ARG;
+}
+
+// ---- launchers: the grid and the dynamic LDS of one instantiation (ud_launch_lds, ud_common.h: LDS reservation once per device, launch,
+// check).  Each one states which template arguments its kernel is instantiated for; any other combination has no kernel and answers
+// UD_ERR_UNSUPPORTED -- never a substitute.
+constexpr bool is_dense_f16_f32_qkv(int epi, int amode) { return amode == UD_A_DENSE && (epi == UD_EPI_F16 || epi == UD_EPI_F32 || epi == UD_EPI_QKV); }
+constexpr bool has_large_tile(int epi, int amode) {
+  return amode == UD_A_DENSE ? epi != UD_EPI_HEAD : amode == UD_A_CONV3_ZERO && (epi == UD_EPI_F16 || epi == UD_EPI_F32);
+}
+constexpr bool has_ln_consumer(int epi, int amode) { return amode == UD_A_DENSE && (epi == UD_EPI_F16 || epi == UD_EPI_QKV); }
+
+template <class C, int EPI, int AMODE, int NST = 2, bool SPLIT = false>
+int launch128(const UdGemm& d, hipStream_t s) {
+  constexpr bool plain = EPI == UD_EPI_F16   ? AMODE <= UD_A_CONV3_REFLECT
+                         : EPI == UD_EPI_F32 ? AMODE <= UD_A_CONV3_ZERO
+                         : EPI == UD_EPI_QKV ? AMODE == UD_A_DENSE && C::BN == 128
+                         : EPI == UD_EPI_D2S ? AMODE == UD_A_DENSE
+                                             : AMODE == UD_A_CONV3_REFLECT && C::BN == 32;     // UD_EPI_HEAD
+  if constexpr (NST == 2 ? plain : C::BN == 128 && is_dense_f16_f32_qkv(EPI, AMODE) && !(SPLIT && EPI == UD_EPI_QKV)) {
+    const int tiles = ((d.N + C::BN - 1) / C::BN) * ((d.M + C::BM - 1) / C::BM);
+    // SPLIT: two-way K split across CUs: twice the workgroups, i.e. twice the DMA bytes in flight
+    const dim3 grid((SPLIT ? 2 : 1) * tiles, 1, d.groups > 0 ? d.groups : 1);
+    return ud_launch_lds<gemm_kernel<C, EPI, AMODE, NST, SPLIT>>(
+        grid, dim3(256), NST * C::STAGE_BYTES, s, NST == 2 ? "ud_gemm_f16 launch" : SPLIT ? "ud_gemm_f16 (4-stage ring, K split) launch" : "ud_gemm_f16 (4-stage ring) launch", d);
+  }
+  return UD_ERR_UNSUPPORTED;
+}
+
+template <int MH, int EPI, int AMODE, bool LNC, bool GRP, bool W3>
+int launch256(const UdGemm& d, hipStream_t s) {
+  if constexpr (has_large_tile(EPI, AMODE) && (!LNC || (has_ln_consumer(EPI, AMODE) && !GRP)) && (!GRP || (MH == 4 && is_dense_f16_f32_qkv(EPI, AMODE))) &&
+                (!W3 || (MH == 3 && AMODE == UD_A_DENSE && !GRP))) {
+    const int tiles = ((d.N + 255) >> 8) * ((d.M + BigCfg<MH>::BM - 1) / BigCfg<MH>::BM);
+    const int lds = (W3 ? 2 * BigCfg<MH>::A_BYTES + 3 * 32768 : 2 * BigCfg<MH>::STAGE) + (LNC ? LNC_LDS : 0) + (EPI == UD_EPI_F32 ? 64 : 0);
+    return ud_launch_lds<gemm256_kernel<MH, EPI, AMODE, false, LNC, GRP, W3>>(
+        dim3(tiles < 256 ? tiles : 256), dim3(512), lds, s, W3 ? "ud_gemm_f16 (large tile, 3-deep weight ring) launch" : "ud_gemm_f16 (large tile) launch", d);
+  }
+  return UD_ERR_UNSUPPORTED;
+}
+
+template <int EPI, int AMODE, bool LNC>
+int launch256bal(const UdGemm& d, hipStream_t s) {
+  if constexpr (has_large_tile(EPI, AMODE) && EPI != UD_EPI_D2S && (!LNC || has_ln_consumer(EPI, AMODE))) {
+    const int tiles_n = (d.N + 255) >> 8;
+    return ud_launch_lds<gemm256_kernel<4, EPI, AMODE, true, LNC>>(dim3(bal_cpc(d) * tiles_n), dim3(512), 2 * BigCfg<4>::STAGE + (LNC ? LNC_LDS : 0), s,
+                                                                   "ud_gemm_f16 (large tile, row-balanced) launch", d);
+  }
+  return UD_ERR_UNSUPPORTED;
+}
+
+template <int EPI, int AMODE>
+int launch256sk(const UdGemm& d, hipStream_t s) {
+  if constexpr (has_large_tile(EPI, AMODE) && (EPI == UD_EPI_F16 || EPI == UD_EPI_F32)) {
+    const int tiles = ((d.N + 255) >> 8) * ((d.M + 191) / 192);         // each over one half of K
+    return ud_launch_lds<gemm256_kernel<3, EPI, AMODE, false, false, false, false, true>>(dim3(2 * tiles), dim3(512), 2 * BigCfg<3>::STAGE + 64, s,
+                                                                                          "ud_gemm_f16 (large tile, K split) launch", d);
+  }
+  return UD_ERR_UNSUPPORTED;
+}
+
+constexpr int UPS_LDS = (UPS_PATCH * UPS_PATCH * 128 + 1023) / 1024 * 1024;     // source patch of the fused up-sampling loader
+template <int NT, int EPI, int AMODE>
+int launch_conv_tile(const UdGemm& d, hipStream_t s) {
+  constexpr bool REFLECT = AMODE >= UD_A_CONV3_REFLECT, UPS = AMODE == UD_A_CONV3_REFLECT_UP;
+  if constexpr (EPI == UD_EPI_HEAD ? NT == 2 && REFLECT : EPI == UD_EPI_F16 && (AMODE == UD_A_CONV3_ZERO || AMODE == UD_A_CONV3_REFLECT)) {
+    const dim3 grid(((d.Wimg + 15) >> 4) * ((d.Himg + 15) >> 4), d.M / d.rows_img, d.groups > 0 ? d.groups : 1);
+    return ud_launch_lds<conv_tile_kernel<NT, EPI, REFLECT, UPS>>(grid, dim3(256), HALO_BYTES + 2 * NT * 16 * 128 + (UPS ? UPS_LDS : 0), s,
+                                                                  "ud_gemm_f16 (halo-tile conv) launch", d);
+  }
+  return UD_ERR_UNSUPPORTED;
+}
+
+int launch_head_regw(const UdGemm& d, hipStream_t s) {
+  const int B = d.M / d.rows_img;
+  const int tiles_x = (d.Wimg + 15) >> 4, tiles_img = tiles_x * ((d.Himg + 15) >> 4), tiles_g = tiles_img * B;
+  const int G = d.groups > 0 ? d.groups : 1;
+  int wgs = (512 + G - 1) / G;                             // two workgroups per CU over all branches
+  wgs = wgs < tiles_g ? wgs : tiles_g;
+  return ud_launch_lds<conv_head_regw_kernel>(dim3(wgs, G), dim3(256), HALO_BYTES + UPS_LDS, s, "ud_gemm_f16 (head conv, register-resident weights) launch", d, tiles_x,
+                                              tiles_img, tiles_g);
+}
+
+// f(IntTag<epi>, IntTag<amode>) with the descriptor's epilogue and A mode as compile-time values
+template <class F>
+int with_epi_amode(const UdGemm& d, F f) {
+  const auto with_amode = [&](auto epi) {
+    switch (d.amode) {
+      case UD_A_DENSE: return f(epi, IntTag<UD_A_DENSE>{});
+      case UD_A_CONV3_ZERO: return f(epi, IntTag<UD_A_CONV3_ZERO>{});
+      case UD_A_CONV3_REFLECT: return f(epi, IntTag<UD_A_CONV3_REFLECT>{});
+      case UD_A_CONV3_REFLECT_UP: return f(epi, IntTag<UD_A_CONV3_REFLECT_UP>{});
+    }
+    return (int)UD_ERR_UNSUPPORTED;
+  };
+  switch (d.epi) {
+    case UD_EPI_F16: return with_amode(IntTag<UD_EPI_F16>{});
+    case UD_EPI_F32: return with_amode(IntTag<UD_EPI_F32>{});
+    case UD_EPI_QKV: return with_amode(IntTag<UD_EPI_QKV>{});
+    case UD_EPI_D2S: return with_amode(IntTag<UD_EPI_D2S>{});
+    case UD_EPI_HEAD: return with_amode(IntTag<UD_EPI_HEAD>{});
+  }
+  return (int)UD_ERR_UNSUPPORTED;
+}
+
+// Names the instantiation of a route and launches it.  No eligibility test in here: the route's attributes select, nothing else.
+int launch_route(const Route& r, const UdGemm& desc, hipStream_t s) {
+  const UdGemm& d = r.grp ? r.merged : desc;
+  const int rc = with_epi_amode(d, [&](auto epi, auto amode) -> int {
+    constexpr int EPI = decltype(epi)::value, AMODE = decltype(amode)::value;
+    switch (r.sched) {
+      case S_TILE128:
+        return r.bn == 128  ? launch128<Cfg<128, 64, 64>, EPI, AMODE>(d, s)
+               : r.bn == 64 ? launch128<Cfg<64, 64, 32>, EPI, AMODE>(d, s)
+                            : launch128<Cfg<32, 32, 32>, EPI, AMODE>(d, s);
+      case S_RING: return r.splitk ? launch128<Cfg<128, 64, 64>, EPI, AMODE, 4, true>(d, s) : launch128<Cfg<128, 64, 64>, EPI, AMODE, 4>(d, s);
+      case S_LIST:
+        if (r.grp) return launch256<4, EPI, AMODE, false, true, false>(d, s);
+        if (r.mh == 4) return r.lnc ? launch256<4, EPI, AMODE, true, false, false>(d, s) : launch256<4, EPI, AMODE, false, false, false>(d, s);
+        if (r.w3) return r.lnc ? launch256<3, EPI, AMODE, true, false, true>(d, s) : launch256<3, EPI, AMODE, false, false, true>(d, s);
+        return r.lnc ? launch256<3, EPI, AMODE, true, false, false>(d, s) : launch256<3, EPI, AMODE, false, false, false>(d, s);
+      case S_BALANCED: return r.lnc ? launch256bal<EPI, AMODE, true>(d, s) : launch256bal<EPI, AMODE, false>(d, s);
+      case S_LIST_SPLITK: return launch256sk<EPI, AMODE>(d, s);
+      case S_PINGPONG: return ud_gemm_pp_launch(d, s);
+      case S_DUO: return ud_gemm_duo_launch(d, s, r.prio);
+      case S_CONV_TILE: return r.nt == 4 ? launch_conv_tile<4, EPI, AMODE>(d, s) : launch_conv_tile<2, EPI, AMODE>(d, s);
+      case S_HEAD_REGW: return launch_head_regw(d, s);
+    }
+    return UD_ERR_UNSUPPORTED;
+  });
+  if (rc == UD_ERR_UNSUPPORTED) ud_set_error("ud_gemm_f16: unsupported epi/amode combination");
+  return rc;
+}
+
 }  // namespace
 
 extern "C" int ud_gemm_f16(const UdGemm* desc, void* stream) {
   UdGemm dcopy = *desc;
-  if ((ud_debug_flags_host() & 4) && (dcopy.epi == UD_EPI_F16 || dcopy.epi == UD_EPI_QKV)) dcopy.ldc2 |= (1 << 30);
-  if (ud_debug_flags_host() & 8) dcopy.tile_hint = 1;                                  // bisect: 128x128 tiles only                               // bisect: no LDS-staged stores
+  if ((ud_debug_flags_host() & 4) && (dcopy.epi == UD_EPI_F16 || dcopy.epi == UD_EPI_QKV)) dcopy.ldc2 |= (1 << 30);     // bisect: no LDS-staged stores
+  if (ud_debug_flags_host() & 8) dcopy.tile_hint = UD_HINT_TILE128;                                                  // bisect: 128x128 tiles only
   const UdGemm& d = dcopy;
-  hipStream_t s = (hipStream_t)stream;
   if (!d.A || !d.W || !d.out || d.M <= 0 || d.N <= 0 || d.K <= 0 || (d.K & 63) || (d.N & 3)) {
     ud_set_error("ud_gemm_f16: bad argument (need K % 64 == 0, N % 4 == 0)");
     return UD_ERR_BAD_ARG;
   }
+  const Route r = route(d);
+  // does the tile-shape model give this problem to the large-tile kernels? (dense A and zero-padded taps; the other A modes have none)
+  const bool large = r.large && (d.amode == UD_A_DENSE || d.amode == UD_A_CONV3_ZERO);
+  const bool halo = r.sched == S_CONV_TILE || r.sched == S_HEAD_REGW;
   if (d.a_wrap < 0 || d.w_wrap < 0 || (d.amode == UD_A_DENSE ? (d.a_wrap & 63) : (d.a_wrap & 7)) || (d.w_wrap & 63) ||
       (d.a_wrap && d.w_wrap) || (d.w_wrap && d.amode != UD_A_DENSE) || (d.a_wrap && d.amode == UD_A_DENSE && 2 * d.a_wrap < d.K) ||
       (d.w_wrap && 2 * d.w_wrap < d.K) || (d.a_wrap && d.amode != UD_A_DENSE && 2 * d.a_wrap < d.Cin) ||
@@ -2267,8 +2348,7 @@ extern "C" int ud_gemm_f16(const UdGemm* desc, void* stream) {
     return UD_ERR_BAD_ARG;
   }
   if (d.row_stats_in) {
-    const int bt = d.amode == UD_A_DENSE ? pick_tiles(d) : 0;
-    if (d.amode != UD_A_DENSE || (d.epi != UD_EPI_F16 && d.epi != UD_EPI_QKV) || !d.wsum || d.add || d.rows_in || (d.N & 15) || bt == 0) {
+    if (d.amode != UD_A_DENSE || (d.epi != UD_EPI_F16 && d.epi != UD_EPI_QKV) || !d.wsum || d.add || d.rows_in || (d.N & 15) || !large) {
       ud_set_error("ud_gemm_f16: LayerNorm-folded consumer (row_stats_in) needs dense A, an fp16 epilogue without add / row remap, wsum, N % 16 == 0 "
                    "and a problem the large-tile kernel takes (ud_gemm_pick >= 3)");
       return UD_ERR_UNSUPPORTED;
@@ -2279,12 +2359,11 @@ extern "C" int ud_gemm_f16(const UdGemm* desc, void* stream) {
     return UD_ERR_UNSUPPORTED;
   }
   if (d.row_stats_out) {
-    const int bt = d.amode == UD_A_DENSE || d.amode == UD_A_CONV3_ZERO ? pick_tiles(d) : 0;
-    if (d.epi != UD_EPI_F32 || (d.N & 63) || (bt == 0 && (d.N <= 64 || d.groups > 1))) {
+    if (d.epi != UD_EPI_F32 || (d.N & 63) || (!large && (d.N <= 64 || d.groups > 1))) {
       ud_set_error("ud_gemm_f16: row_stats_out needs the fp32 epilogue, N % 64 == 0 and 64-column wave tiles (N > 64, no groups)");
       return UD_ERR_UNSUPPORTED;
     }
-    if (d.row_stats_final && (bt == 0 || !d.row_stats_ticket || d.ln_D <= 0 || d.N > 1024 || (d.N & 127) || d.groups > 1)) {
+    if (d.row_stats_final && (!large || !d.row_stats_ticket || d.ln_D <= 0 || d.N > 1024 || (d.N & 127) || d.groups > 1)) {
       ud_set_error("ud_gemm_f16: row_stats_final (in-kernel reduction of the row statistics) needs the large-tile kernel, a ticket buffer, ln_D, "
                    "N <= 1024 and N % 128 == 0 (the finalizer reads the 64-column slabs in pairs)");
       return UD_ERR_UNSUPPORTED;
@@ -2301,19 +2380,11 @@ extern "C" int ud_gemm_f16(const UdGemm* desc, void* stream) {
     ud_set_error("ud_gemm_f16: bad conv geometry");
     return UD_ERR_BAD_ARG;
   }
-  if (d.epi == UD_EPI_QKV) {
-    if (d.amode != UD_A_DENSE || !d.out2 || (d.vsplit % 128) || (d.tok_per_img & 3) || (d.kv_ld & 3) || d.N <= 64) {
-      ud_set_error("ud_gemm_f16: bad QKV epilogue geometry");
-      return UD_ERR_BAD_ARG;
-    }
-    {
-      UdGemm mg;
-      if (grouped_as_big(d, mg)) return launch256<4, UD_EPI_QKV, UD_A_DENSE, false, true>(mg, s);
-    }
-    if (const int bt = pick_tiles(d)) return launch_big<UD_EPI_QKV>(d, s, bt);
-    return launch<Cfg<128, 64, 64>, UD_EPI_QKV, UD_A_DENSE>(d, s);
+  if (d.epi == UD_EPI_QKV && (d.amode != UD_A_DENSE || !d.out2 || (d.vsplit % 128) || (d.tok_per_img & 3) || (d.kv_ld & 3) || d.N <= 64)) {
+    ud_set_error("ud_gemm_f16: bad QKV epilogue geometry");
+    return UD_ERR_BAD_ARG;
   }
-  if (d.up_src && d.epi != UD_EPI_D2S) {
+  if (d.up_src && d.epi != UD_EPI_D2S && d.epi != UD_EPI_QKV) {      // (the QKV epilogue has never looked at it)
     ud_set_error("ud_gemm_f16: up_src belongs to the D2S epilogue");
     return UD_ERR_BAD_ARG;
   }
@@ -2328,8 +2399,6 @@ extern "C" int ud_gemm_f16(const UdGemm* desc, void* stream) {
                    "up_ld >= d2s_Co, up_img_rows >= up_H * up_W");
       return UD_ERR_BAD_ARG;
     }
-    if (const int bt = pick_tiles(d)) return launch_big<UD_EPI_D2S>(d, s, bt);
-    return dispatch_bn<UD_EPI_D2S, UD_A_DENSE>(d, s);
   }
   if (d.epi == UD_EPI_HEAD) {
     if ((d.amode != UD_A_CONV3_REFLECT && d.amode != UD_A_CONV3_REFLECT_UP) || d.N != 32 || !d.w2 || !d.bias) {
@@ -2339,58 +2408,13 @@ extern "C" int ud_gemm_f16(const UdGemm* desc, void* stream) {
     if (d.amode == UD_A_CONV3_REFLECT_UP) {
       // the loader stages a source patch of at most UPS_PATCH^2 pixels per 16 x 16 tile: 17 * scale + 3 <= UPS_PATCH
       const bool fits = 17.0 * (d.Hsrc - 1) / (d.Himg > 1 ? d.Himg - 1 : 1) + 3.0 <= UPS_PATCH && 17.0 * (d.Wsrc - 1) / (d.Wimg > 1 ? d.Wimg - 1 : 1) + 3.0 <= UPS_PATCH;
-      if (!conv_tile_ok(d) || d.Hsrc < 1 || d.Wsrc < 1 || (d.cstride & 7) || !fits) {
+      if (!halo || d.Hsrc < 1 || d.Wsrc < 1 || (d.cstride & 7) || !fits) {
         ud_set_error("ud_gemm_f16: CONV3_REFLECT_UP needs Cin % 64 == 0, dense images, Hsrc / Wsrc >= 1 and an up-sampling factor >= ~1.7");
         return UD_ERR_BAD_ARG;
       }
-      if (d.Cin == 64 && head_regw_enabled()) {
-        // weights in registers, persistent workgroups (conv_head_regw_kernel); UD_HEAD_REGW=0 keeps the LDS-streamed form (A/B)
-        const int lds = HALO_BYTES + (UPS_PATCH * UPS_PATCH * 128 + 1023) / 1024 * 1024;
-        static bool attr_set[UD_MAX_DEVICES];
-        if (!ud_attr_once(attr_set)) (void)hipFuncSetAttribute((const void*)conv_head_regw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        const int B = d.M / d.rows_img;
-        const int tiles_x = (d.Wimg + 15) >> 4, tiles_img = tiles_x * ((d.Himg + 15) >> 4), tiles_g = tiles_img * B;
-        const int G = d.groups > 0 ? d.groups : 1;
-        int wgs = (512 + G - 1) / G;                             // two workgroups per CU over all branches
-        wgs = wgs < tiles_g ? wgs : tiles_g;
-        hipLaunchKernelGGL(conv_head_regw_kernel, dim3(wgs, G), dim3(256), lds, s, d, tiles_x, tiles_img, tiles_g);
-        UD_CHECK_LAUNCH("ud_gemm_f16 (head conv, register-resident weights) launch");
-        return UD_OK;
-      }
-      return launch_conv_tile<2, UD_EPI_HEAD, true, true>(d, s);
     }
-    if (conv_tile_ok(d)) return launch_conv_tile<2, UD_EPI_HEAD, true>(d, s);
-    return launch<Cfg<32, 32, 32>, UD_EPI_HEAD, UD_A_CONV3_REFLECT>(d, s);
   }
-  if (d.epi == UD_EPI_F16) {
-    if (conv_tile_ok(d)) {
-      if (d.amode == UD_A_CONV3_REFLECT) return d.N == 64 ? launch_conv_tile<4, UD_EPI_F16, true>(d, s) : launch_conv_tile<2, UD_EPI_F16, true>(d, s);
-      return d.N == 64 ? launch_conv_tile<4, UD_EPI_F16, false>(d, s) : launch_conv_tile<2, UD_EPI_F16, false>(d, s);
-    }
-    {
-      UdGemm mg;
-      if (grouped_as_big(d, mg)) return launch256<4, UD_EPI_F16, UD_A_DENSE, false, true>(mg, s);
-    }
-    if (const int bt = pick_tiles(d))
-      return d.amode == UD_A_DENSE ? launch_big<UD_EPI_F16>(d, s, bt) : launch_big<UD_EPI_F16, UD_A_CONV3_ZERO>(d, s, bt);
-    if (d.amode == UD_A_DENSE) return dispatch_bn<UD_EPI_F16, UD_A_DENSE>(d, s);
-    if (d.amode == UD_A_CONV3_ZERO) return dispatch_bn<UD_EPI_F16, UD_A_CONV3_ZERO>(d, s);
-    return dispatch_bn<UD_EPI_F16, UD_A_CONV3_REFLECT>(d, s);
-  }
-  if (d.epi == UD_EPI_F32) {
-    {
-      UdGemm mg;
-      if (grouped_as_big(d, mg)) return launch256<4, UD_EPI_F32, UD_A_DENSE, false, true>(mg, s);
-    }
-    if (d.tile_hint >= 12 && d.tile_hint <= 14 && ud_gemm_duo_ok(d)) return ud_gemm_duo_launch(d, s, d.tile_hint == 12 ? 1 : d.tile_hint == 13 ? 0 : 2);
-    if (pp_pick(d)) return ud_gemm_pp_launch(d, s);
-    if (const int bt = pick_tiles(d))
-      return d.amode == UD_A_DENSE ? launch_big<UD_EPI_F32>(d, s, bt) : launch_big<UD_EPI_F32, UD_A_CONV3_ZERO>(d, s, bt);
-    if (d.amode == UD_A_DENSE) return dispatch_bn<UD_EPI_F32, UD_A_DENSE>(d, s);
-    if (d.amode == UD_A_CONV3_ZERO) return dispatch_bn<UD_EPI_F32, UD_A_CONV3_ZERO>(d, s);
-  }
-  ud_set_error("ud_gemm_f16: unsupported epi/amode combination");
-  return UD_ERR_UNSUPPORTED;
+  return launch_route(r, d, (hipStream_t)stream);
 }
 
 #ifdef UD_TRACE
@@ -2399,27 +2423,9 @@ extern "C" int ud_trace_set(void* buf) {
 }
 #endif
 
-// Which kernel ud_gemm_f16 would launch for this descriptor (for profiling labels): 0/1/2 = 128-row kernels with BN 128/64/32,
-// 3 = 192x256 tiles, 4 = 256x256 tiles, 5 = halo-tile conv, 6 / 7 = 128x128 pipelined ring without / with the K split, 8 = row-balanced,
-// 10 = 192x256 tiles with the two-way K split, 11 = 192x256 tiles in the ping-pong form (gemm_pp.hip);
-// + 16 when the folded-LayerNorm consumer instantiation runs (row_stats_in), + 32 for a grouped problem run as one large-tile launch.
-extern "C" int ud_gemm_pick(const UdGemm* desc) {
-  const UdGemm& d = *desc;
-  {
-    UdGemm mg;
-    if ((d.epi == UD_EPI_F16 || d.epi == UD_EPI_F32 || d.epi == UD_EPI_QKV) && grouped_as_big(d, mg)) return 4 + 32;
-  }
-  if (conv_tile_ok(d) && (d.epi == UD_EPI_HEAD || d.epi == UD_EPI_F16)) return 5;
-  if (d.epi == UD_EPI_F32 && d.tile_hint >= 12 && d.tile_hint <= 14 && ud_gemm_duo_ok(d)) return 12;
-  if (d.epi == UD_EPI_F32 && pp_pick(d)) return 11;
-  if (d.epi != UD_EPI_HEAD) {
-    int bt = pick_tiles(d);
-    if (bt == 8 && d.row_stats_final) bt = 3;          // launch_big: the in-kernel statistics reduction runs on the 192-row tile list
-    if (bt) return bt + (d.row_stats_in ? 16 : 0);
-  }
-  if (d.N > 64 && d.epi != UD_EPI_D2S) {
-    const int v = ring_variant(d);
-    if (v) return 5 + v;
-  }
-  return d.N > 64 ? 0 : (d.N > 32 ? 1 : 2);
+extern "C" int ud_gemm_pick(const UdGemm* desc) { return pick_code(route(*desc)); }
+
+extern "C" int ud_gemm_kernel_name(const UdGemm* desc, char* buf, int cap) {
+  if (!desc || !buf || cap <= 0) return UD_ERR_BAD_ARG;
+  return kernel_name(route(*desc), *desc, buf, cap);
 }

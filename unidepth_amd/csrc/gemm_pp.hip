@@ -365,16 +365,7 @@ int ud_gemm_pp_launch(const UdGemm& d, hipStream_t s) {
   constexpr int MQ = 3;
   constexpr int LDS = 2 * (64 * MQ * 128 + 32768) + 64;
   const int tiles = (d.N >> 8) * ((d.M + 64 * MQ - 1) / (64 * MQ));
-  static bool attr_set[UD_MAX_DEVICES];
-  if (!ud_attr_once(attr_set)) {
-    if (hipFuncSetAttribute((const void*)gemm_pp_f32_kernel<MQ, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      ud_set_error("ud_gemm_f16: cannot reserve the LDS buffers of the ping-pong large-tile kernel");
-      return UD_ERR_LAUNCH;
-    }
-  }
-  hipLaunchKernelGGL((gemm_pp_f32_kernel<MQ, 8>), dim3(tiles < 256 ? tiles : 256), dim3(512), LDS, s, d, 0);
-  UD_CHECK_LAUNCH("ud_gemm_f16 (large tile, ping-pong) launch");
-  return UD_OK;
+  return ud_launch_lds<gemm_pp_f32_kernel<MQ, 8>>(dim3(tiles < 256 ? tiles : 256), dim3(512), LDS, s, "ud_gemm_f16 (large tile, ping-pong) launch", d, 0);
 }
 
 // the two-workgroups-per-CU form: 192 x 128 tiles, one round of at most 512
@@ -388,14 +379,5 @@ int ud_gemm_duo_launch(const UdGemm& d, hipStream_t s, int prio_mode) {
   constexpr int MQ = 3;
   constexpr int LDS = 2 * (64 * MQ * 128 + 16384);          // 81 920 B: exactly half of a CU's LDS
   const int tiles = (d.N >> 7) * ((d.M + 64 * MQ - 1) / (64 * MQ));
-  static bool attr_set[UD_MAX_DEVICES];
-  if (!ud_attr_once(attr_set)) {
-    if (hipFuncSetAttribute((const void*)gemm_pp_f32_kernel<MQ, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      ud_set_error("ud_gemm_f16: cannot reserve the LDS buffers of the two-workgroups-per-CU kernel");
-      return UD_ERR_LAUNCH;
-    }
-  }
-  hipLaunchKernelGGL((gemm_pp_f32_kernel<MQ, 4>), dim3(tiles), dim3(256), LDS, s, d, prio_mode);
-  UD_CHECK_LAUNCH("ud_gemm_f16 (two workgroups per CU) launch");
-  return UD_OK;
+  return ud_launch_lds<gemm_pp_f32_kernel<MQ, 4>>(dim3(tiles), dim3(256), LDS, s, "ud_gemm_f16 (two workgroups per CU) launch", d, prio_mode);
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include "../../include/unidepth_hip.h"
 
 typedef _Float16 half_t;
@@ -93,3 +94,19 @@ static inline int ud_debug_flags_host() { return 0; }
       return UD_ERR_LAUNCH;                            \
     }                                                  \
   } while (0)
+
+// Launch of a kernel whose dynamic LDS may exceed the default limit: reserve it once per (kernel, device), launch, check.  A refused
+// reservation is an error (the launch behind it would fail anyway).  `what` names the launch in the error message.
+template <auto KERNEL, class... Args>
+int ud_launch_lds(dim3 grid, dim3 block, int lds, hipStream_t s, const char* what, const Args&... args) {
+  static bool attr_set[UD_MAX_DEVICES];
+  if (!ud_attr_once(attr_set) && hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: cannot reserve %d bytes of LDS", what, lds);
+    ud_set_error(msg);
+    return UD_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(KERNEL, grid, block, lds, s, args...);
+  UD_CHECK_LAUNCH(what);
+  return UD_OK;
+}

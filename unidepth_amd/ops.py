@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import (UD_A_CONV3_REFLECT, UD_A_CONV3_REFLECT_UP, UD_A_CONV3_ZERO, UD_A_DENSE, UD_ACT_GELU, UD_ACT_LRELU, UD_ACT_NONE,  # noqa: F401
-                   UD_EPI_D2S, UD_EPI_F16, UD_EPI_F32, UD_EPI_HEAD, UD_EPI_QKV, UdAttention, UdFinalize, UdGemm,
+                   UD_EPI_D2S, UD_EPI_F16, UD_EPI_F32, UD_EPI_HEAD, UD_EPI_QKV, UD_PICK_LARGE_TILE, UD_PICK_SCHEDULE, UdAttention, UdFinalize, UdGemm,
                    UdCameraHead, UdCamPhase, UdDwConv7, UdLayerNorm, UdLinearF32, UdPreprocess, UdRayEmbed, UdResizeAC, UdUpsample2x, check, lib)
 
 
@@ -41,6 +41,13 @@ def mk(struct, **kw):
 def gemm_pick(**kw) -> int:
     """The schedule ud_gemm_f16 would run this descriptor on (include/unidepth_hip.h ud_gemm_pick).  Host-side, nothing is launched."""
     return lib.ud_gemm_pick(C.byref(mk(UdGemm, **kw)))
+
+
+def gemm_kernel_name(desc) -> str:
+    """Kernel class (name with template arguments) of the schedule ud_gemm_f16 runs this UdGemm on.  Host-side, nothing is launched."""
+    buf = C.create_string_buffer(96)
+    check(lib.ud_gemm_kernel_name(C.byref(desc), buf, len(buf)), "ud_gemm_kernel_name")
+    return buf.value.decode()
 
 
 def camera_head_desc(phases, T, H, Cc, scale, eps, sync_ws, workgroups=0, fail_host=None, spin_limit=0):
@@ -163,27 +170,8 @@ class Program:
             kw["splitk_ws"], kw["splitk_cnt"] = self._splitk[1]
             kw["splitk_ws_bytes"] = self._splitk[1][0].numel() * 4
         d = mk(UdGemm, **kw)
-        pick, epi, amode = lib.ud_gemm_pick(C.byref(d)), kw.get("epi", 0), kw.get("amode", 0)
-        lnc, grp = "true" if pick & 16 else "false", "true" if pick & 32 else "false"
-        pick &= 15
-        if pick <= 2:       # names as rocprofv3 prints them (template arguments), so profiles and bench lines can be joined
-            cls = "gemm_kernel<Cfg<%s>, %d, %d, 2, false>" % (("128, 64, 64", "64, 64, 32", "32, 32, 32")[pick], epi, amode)
-        elif pick in (6, 7):     # 128x128 tiles, 4-stage pipelined ring (7: + two-way K split)
-            cls = "gemm_kernel<Cfg<128, 64, 64>, %d, %d, 4, %s>" % (epi, amode, "true" if pick == 7 else "false")
-        elif pick <= 4:
-            # 7th template argument: the 3-deep weight ring of the 192-row tile list (csrc/gemm.hip launch256: dense A, not grouped, K >= 128)
-            w3 = pick == 3 and amode == UD_A_DENSE and grp == "false" and kw["K"] >= 128 and kw.get("tile_hint", 0) != 9
-            cls = "gemm256_kernel<%d, %d, %d, false, %s, %s, %s, false>" % (pick, epi, amode, lnc, grp, "true" if w3 else "false")
-        elif pick == 8:     # row-balanced schedule of the 256-column kernel
-            cls = "gemm256_kernel<4, %d, %d, true, %s, false, false, false>" % (epi, amode, lnc)
-        elif pick == 11:    # 192-row tiles, ping-pong schedule (csrc/gemm_pp.hip)
-            cls = "gemm_pp_f32_kernel<3, 8>"
-        elif pick == 10:    # 192-row tile list, two-way K split (2 * tiles workgroups)
-            cls = "gemm256_kernel<3, %d, %d, false, false, false, false, true>" % (epi, amode)
-        elif amode == 3 and kw.get("Cin", 0) == 64 and epi == UD_EPI_HEAD:
-            cls = "conv_head_regw_kernel"                       # head conv with its weights in registers
-        else:
-            cls = "conv_tile_kernel<%d, %d, %s, %s>" % (n // 16, epi, "true" if amode >= 2 else "false", "true" if amode == 3 else "false")
+        epi, amode = kw.get("epi", 0), kw.get("amode", 0)
+        cls = gemm_kernel_name(d)       # as rocprofv3 prints it (template arguments), so profiles and bench lines can be joined
         self.keep.extend(v for v in kw.values() if isinstance(v, torch.Tensor))
         # algorithmic HBM bytes (every operand element once): A (conv modes: the image, not the 9x gathered rows), W, outputs,
         # + the old fp32 values of an accumulating epilogue

@@ -9,7 +9,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .ops import UD_ACT_GELU, UD_EPI_F16, UD_EPI_F32, UD_EPI_QKV
+from .ops import UD_ACT_GELU, UD_EPI_F16, UD_EPI_F32, UD_EPI_QKV, UD_PICK_LARGE_TILE, UD_PICK_SCHEDULE
 from .weights import _rup
 
 
@@ -87,7 +87,7 @@ class PlanRecorder:
             tickets = torch.zeros(2, M // 128 + 2, dtype=torch.int32, device=self.dev)     # one set per producer (proj, fc2): a set counts arrivals of ONE tiling
             big = all(ops.gemm_pick(A=xn, W=w[f"enc.0.{nm}.w"], out=xn, M=M, N=n_, K=k_, lda=k_, ldw=k_, ldc=n_, epi=e_, vsplit=2 * D, tok_per_img=Np,
                                     kv_ld=Nkp, heads_v=heads, out2=vt, accumulate=int(e_ == UD_EPI_F32),
-                                    **(dict(row_stats_in=rstats, wsum=w[f"enc.0.{nm}.wsum"]) if nm in ("qkv", "fc1") else {})) & 15 in (3, 4, 8)
+                                    **(dict(row_stats_in=rstats, wsum=w[f"enc.0.{nm}.wsum"]) if nm in ("qkv", "fc1") else {})) & UD_PICK_SCHEDULE in UD_PICK_LARGE_TILE
                       for nm, n_, k_, e_ in (("qkv", 3 * D, D, UD_EPI_QKV), ("proj", D, D, UD_EPI_F32), ("fc1", 4 * D, D, UD_EPI_F16), ("fc2", D, 4 * D, UD_EPI_F32)))
             fold = big and allow_fold
             lnc = dict(row_stats_in=rstats, ln_slabs=slabs, ln_D=D, ln_eps=1e-6)

@@ -375,7 +375,7 @@ class _EncPlan(PlanRecorder):
         fc1 = dict(out=hid, M=rows, N=4 * C, lda=C, ldc=4 * C, epi=UD_EPI_F16, act=UD_ACT_GELU, **_wk(w[f"blk.{s}.0.fc1.w"], C))
         rstats = z(rows, 2, dtype=f32)
         fold = (DWLN and C % 64 == 0 and C // 64 <= 16 and f"blk.{s}.0.fc1.wsum" in w and
-                (ops.gemm_pick(A=xh, W=w[f"blk.{s}.0.fc1.w"], bias=w[f"blk.{s}.0.fc1.b"], row_stats_in=rstats, wsum=w[f"blk.{s}.0.fc1.wsum"], **fc1) & 15) in (3, 4, 8))
+                (ops.gemm_pick(A=xh, W=w[f"blk.{s}.0.fc1.w"], bias=w[f"blk.{s}.0.fc1.b"], row_stats_in=rstats, wsum=w[f"blk.{s}.0.fc1.wsum"], **fc1) & L.UD_PICK_SCHEDULE) in L.UD_PICK_LARGE_TILE)
         self.dwln.append(bool(fold))
         dw = dict(B=B, H=H, W=W, C=C, ldx=C, ldy=C, tag=f"dwconv.s{s}")
         if fold:
