@@ -110,6 +110,59 @@ def poisoned(data, ld=None, pre_rows=0, post_rows=0, offset_cols=0, fill=None):
     return v
 
 
+# ---- bounds as sums of named terms (the pointwise / resampling kernels, tests/test_pointwise_layouts_gpu.py) ----------------------------
+# assert_elementwise above is one formula for fp32 reduction chains; the kernels outside the GEMM family have other error sources
+# (source coordinates computed in fp32, transcendentals, an fp16 store behind a LayerNorm), so their bound is built per case as a SUM
+# of the terms below, each a tensor shaped like the result, and checked by assert_bound.  Nothing here depends on a kernel's output.
+def term_rounding(mag64, taps):
+    """fp32 products and sums over `taps` terms: C_ACC sqrt(taps) 2^-24 mag, mag = the same expression on absolute values."""
+    return C_ACC * math.sqrt(max(taps, 1)) * 2.0 ** -24 * mag64.double()
+
+
+def term_coord(max_coord, tap_abs_sum64):
+    """Source coordinates computed in fp32: a coordinate near `max_coord` carries ~2^-24 max_coord of rounding per operation (scale,
+    product, floor subtraction), the interpolation weight inherits it, and the result moves by delta_w |v1 - v0| <= delta_w sum |taps|.
+    `mag` can be near zero where the taps cancel, so the term is max_coord 2^-22 sum |tap values|, not a multiple of mag."""
+    return float(max_coord) * 2.0 ** -22 * tap_abs_sum64.double()
+
+
+def term_store_f16(ref64):
+    """Round-to-nearest fp16 store: 2^-11 |ref|, plus half the subnormal spacing."""
+    return 2.0 ** -11 * ref64.double().abs() + 2.0 ** -25
+
+
+def term_store_f32(ref64):
+    """ONE correctly rounded fp32 operation (half a unit in the last place, 2^-24 |ref|) under the factor-4 headroom rule: 2^-22 |ref|."""
+    return 2.0 ** -22 * ref64.double().abs()
+
+
+def bound_ratio(out, ref64, bound64):
+    """max over the elements of |out - ref| / bound (inf where out is NaN or the bound is zero and the error is not)."""
+    o = out.double().reshape(ref64.shape)
+    err = (o - ref64.double()).abs()
+    err = torch.where(torch.isnan(err), torch.full_like(err, math.inf), err)
+    b = bound64.double().expand_as(err)
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / b)
+    return ratio, err
+
+
+def assert_bound(out, ref64, bound64, name="result", margin=1.0):
+    """|out - ref| * margin <= bound for EVERY element; returns the worst error / bound.  margin = 4 is the headroom rule of C_ACC (the
+    clean fp32 evaluation uses at most a quarter of the bound)."""
+    if ref64.numel() == 0:
+        return 0.0
+    ratio, err = bound_ratio(out, ref64, bound64)
+    worst = int(ratio.reshape(-1).argmax())
+    w = float(ratio.reshape(-1)[worst])
+    if not w * margin <= 1.0:
+        idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(worst), ratio.shape))
+        n = int((ratio * margin > 1.0).sum())
+        raise AssertionError(f"{name}: {n} element(s) outside the bound{'' if margin == 1.0 else f' / {margin:g}'}; worst at {idx}: out "
+                             f"{out.double().reshape(ref64.shape).reshape(-1)[worst].item():.8g}, ref {ref64.double().reshape(-1)[worst].item():.8g}, "
+                             f"error {err.reshape(-1)[worst].item():.3g} > bound {bound64.double().expand_as(err).reshape(-1)[worst].item():.3g}")
+    return w
+
+
 def assert_elementwise(out, ref64, mag64, K, fp16_out=False, c=C_ACC, gelu=False, r_mag=0.0, atol=0.0, tile=(16, 16), name="result"):
     """|out - ref| <= r_out |ref| + g (c sqrt(K) 2^-24 + r_mag) mag + atol for EVERY element (g = 1.13 behind GELU, r_out = 2^-11 for fp16
     stores, plus the fp16 subnormal spacing).  On failure: the worst element's (row, column), the tile it falls in and its numbers."""

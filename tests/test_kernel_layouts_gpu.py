@@ -65,6 +65,9 @@ GEMM_CASES = [
     dict(id="ksplit_f16_wrap", pick=7, M=1064, N=1020, K=1024, act=GELU, a_wrap=512, splitk=1),
     dict(id="ksplit_f16_wwrap", pick=7, M=512, N=1064, K=1024, w_wrap=512, splitk=1, lay=((0, 0), (0, 1), (1, 1))),
     dict(id="hint7_f16", pick=7, M=700, N=516, K=512, hint=7, splitk=1),
+    # the two classes only the V1 ViT-L plan records: the split-fp16 token projection behind the row remap (K split), the split-fp16 qkv on plain tiles
+    dict(id="ksplit_f32_remap_add_wrap", pick=7, M=1000, N=384, K=1280, epi=F32, a_wrap=640, remap=(500, 509, 3), add=1, splitk=1),
+    dict(id="bn128_qkv_wrap", pick=0, M=1064, N=3 * 256, K=1024, epi=QKV, B=1, heads=4, a_wrap=512, hint=5),
     # large tiles: 256x256 (2 -> 4), 192x256 (3), row-balanced (8), 2-deep weight ring (9 -> 3), large-tile K split (10)
     dict(id="hint2_f16_gelu", pick=4, M=1100, N=516, K=128, hint=2, act=GELU),
     dict(id="hint2_f32_acc1_out2", pick=4, M=1100, N=516, K=384, hint=2, epi=F32, acc=1, out2=1),

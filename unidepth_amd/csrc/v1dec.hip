@@ -448,7 +448,7 @@ __global__ __launch_bounds__(256) void head_mix_kernel(const float* q, const flo
 __global__ __launch_bounds__(256) void add_kernel(float* dst, const float* a, const float* b, long long n4) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) ((f32x4*)dst)[i] = ((const f32x4*)a)[i] + ((const f32x4*)b)[i];
 }
-// dst[(img * rows_per_img + row_off + t) * ld + d] = src[(img * T + t) * D + d]; cast: 0 fp32 -> fp32, 1 fp32 -> fp16, 2 fp16 -> fp16 transposed pack of T^T
+// dst[(img * rows_per_img + row_off + t) * ld + d] = src[(img * T + t) * D + d]; to_f16: 0 fp32 -> fp32, 1 fp32 -> fp16, 2 fp32 -> the fp16 pair [hi | lo] (ld >= 2 D)
 __global__ __launch_bounds__(256) void copy_rows_kernel(void* dst, const float* src, int n_img, int T, int rows_per_img, int row_off, int D, int ld, int to_f16) {
   const long long total = (long long)n_img * T * D;
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
