@@ -165,7 +165,8 @@ def assert_bound(out, ref64, bound64, name="result", margin=1.0):
 
 def assert_elementwise(out, ref64, mag64, K, fp16_out=False, c=C_ACC, gelu=False, r_mag=0.0, atol=0.0, tile=(16, 16), name="result"):
     """|out - ref| <= r_out |ref| + g (c sqrt(K) 2^-24 + r_mag) mag + atol for EVERY element (g = 1.13 behind GELU, r_out = 2^-11 for fp16
-    stores, plus the fp16 subnormal spacing).  On failure: the worst element's (row, column), the tile it falls in and its numbers."""
+    stores, plus the fp16 subnormal spacing).  On failure: the worst element's (row, column), the tile it falls in and its numbers.
+    Returns the worst error / bound."""
     o = out.double().reshape(ref64.shape[0], -1) if out.dim() != ref64.dim() else out.double()
     ref = ref64.double().reshape(o.shape)
     mag = mag64.double().reshape(o.shape)
@@ -183,3 +184,4 @@ def assert_elementwise(out, ref64, mag64, K, fp16_out=False, c=C_ACC, gelu=False
         raise AssertionError(f"{name}: {n} element(s) outside the bound; worst at (row {r}, column {col}) = tile ({r // tile[0]}, {col // tile[1]}) "
                              f"of {tile[0]}x{tile[1]}: out {o.reshape(-1)[worst].item():.6g}, ref {ref.reshape(-1)[worst].item():.6g}, "
                              f"error {err.reshape(-1)[worst].item():.3g} > bound {bound.reshape(-1)[worst].item():.3g}")
+    return float(excess.reshape(-1)[worst]) if excess.numel() else 0.0

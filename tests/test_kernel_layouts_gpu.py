@@ -6,8 +6,8 @@ judged element by element against the fp64 statement of the op on the same fp16-
 element.  A GEMM case also runs at the product's own (dense) layout: both runs must agree bit for bit, so only the layout changed.
 
 GEMM_CASES is the matrix of GEMM schedules this module covers; each case names the ud_gemm_pick value it reaches (asserted here and, on
-the host, by tests/test_layout_coverage_cpu.py, which also checks that every GEMM descriptor of the recorded V1 / V2 plans falls into a
-class of this table).  The module imports without a GPU."""
+the host, by tests/test_layout_coverage_cpu.py, which also checks that every GEMM descriptor of the recorded V1 / V2 plans -- single-image
+and batched -- falls into a class of this table).  Every run prints `RATIO gemm <case> <layout> <worst error / bound>`.  The module imports without a GPU."""
 import ctypes as C
 import importlib.util
 import math
@@ -107,6 +107,62 @@ GEMM_CASES = [
     dict(id="d2s_k2", pick=0, epi=D2S, M=0, N=4 * 128, K=128, k=2, B=2, Hin=7, Win=9, pad=4, out2=1, act2=LRELU),
     dict(id="head_reflect_groups", pick=2, epi=HEAD, amode=2, M=0, N=32, K=320, Cin=32, H=20, W=13, B=1, pad=0, groups=2),
     dict(id="head_reflect_up_groups", pick=5, epi=HEAD, amode=3, M=0, N=32, K=576, Cin=64, H=46, W=61, Hs=26, Ws=35, B=1, pad=0, groups=2),
+    # ---- the classes only the BATCHED plans record (tests/test_layout_coverage_cpu.py SIGNATURES: M = B x tokens moves the tile choice).
+    # A wrap boundary is an odd multiple of 64 wherever a wrap meets a row remap or groups: it then falls inside the 128-wide K step of the
+    # large-tile kernels, in a launch whose remapped image boundary falls inside a row tile.
+    # 128-row kernels: V1 at batch 2 (split-fp16 token projections behind the row remap), the ViT-B head convolutions (Cin 96, N 48, two branches),
+    # the grouped prompt projection with the split-fp16 weight operand, V2 ViT-S at batch 8 (the token projection behind the row remap)
+    dict(id="bn128_f16_remap_add_wrap", pick=0, M=1000, N=324, K=384, a_wrap=192, remap=(500, 509, 3), add=1),
+    dict(id="bn128_f32_remap_wrap", pick=0, M=1000, N=260, K=384, epi=F32, a_wrap=192, remap=(500, 504, 0)),
+    dict(id="bn128_f32_remap_add", pick=0, M=1000, N=260, K=320, epi=F32, remap=(500, 504, 1), add=1),
+    dict(id="bn128_f16_groups_wwrap", pick=0, M=300, N=324, K=640, w_wrap=320, groups=2, gA0=1, lay=((0, 0), (0, 1), (1, 1))),
+    dict(id="conv_reflect_bn64_groups", pick=1, amode=2, M=0, N=48, K=896, Cin=96, H=13, W=11, B=2, pad=0, groups=2),
+    dict(id="ring_qkv", pick=6, M=1064, N=3 * 256, K=512, epi=QKV, B=1, heads=4),
+    # 192 x 256 tile list: split-fp16 A on every epilogue, implicit-GEMM convolutions, D2S
+    dict(id="hint3_f16_wrap", pick=3, M=1300, N=772, K=384, hint=3, act=GELU, a_wrap=192),
+    dict(id="hint3_f16_remap_add_wrap", pick=3, M=1200, N=516, K=640, hint=3, a_wrap=320, remap=(600, 603, 1), add=1),
+    dict(id="hint3_f32_wrap_acc1_maxo", pick=3, M=1300, N=516, K=384, hint=3, epi=F32, acc=1, maxo=1, a_wrap=192),
+    dict(id="hint3_f32_wrap_gelu_out2", pick=3, M=1300, N=516, K=384, hint=3, epi=F32, act=GELU, out2=1, a_wrap=192),
+    dict(id="hint3_f32_remap_add_wrap", pick=3, M=1200, N=516, K=640, hint=3, epi=F32, a_wrap=320, remap=(600, 603, 1), add=1),
+    dict(id="hint3_qkv_wrap", pick=3, M=2 * 700, N=3 * 256, K=512, hint=3, epi=QKV, B=2, heads=4, a_wrap=256),
+    dict(id="hint3_conv_zero_f16", pick=3, amode=1, M=0, N=320, K=576, Cin=64, H=20, W=27, B=2, pad=4, hint=3, act=LRELU),
+    dict(id="hint3_conv_zero_f32_acc1_out2", pick=3, amode=1, M=0, N=320, K=576, Cin=64, H=20, W=27, B=2, pad=4, hint=3, epi=F32, acc=1, out2=1, act2=LRELU),
+    dict(id="hint3_conv_zero_f32_acc2_out2", pick=3, amode=1, M=0, N=320, K=576, Cin=64, H=20, W=27, B=2, pad=4, hint=3, epi=F32, acc=2, out2=1),
+    dict(id="hint3_conv_zero_f32_wrap", pick=3, amode=1, M=0, N=320, K=1728, Cin=192, H=20, W=27, B=2, pad=4, hint=3, epi=F32, a_wrap=128),
+    # D2S: Co % 64 == 0 takes the straight-line epilogue on full tiles (k >= 2 then has no partial column tile: k k Co % 256 == 0), any other Co the
+    # element-wise one on every tile
+    dict(id="hint3_d2s_k1", pick=3, epi=D2S, M=0, N=320, K=256, k=1, B=2, Hin=20, Win=27, pad=4, hint=3, out2=1, act2=LRELU),
+    dict(id="hint3_d2s_k2", pick=3, epi=D2S, M=0, N=4 * 192, K=128, k=2, B=2, Hin=20, Win=27, pad=4, hint=3, out2=1, act2=LRELU),
+    dict(id="hint3_d2s_k2_co80", pick=3, epi=D2S, M=0, N=4 * 80, K=128, k=2, B=2, Hin=20, Win=27, pad=4, hint=3, out2=1, act2=LRELU),
+    # 256 x 256 tile list
+    dict(id="hint2_f16_wrap", pick=4, M=1100, N=516, K=384, hint=2, act=GELU, a_wrap=192),
+    dict(id="hint2_f16_remap_add_wrap", pick=4, M=1200, N=516, K=640, hint=2, a_wrap=320, remap=(600, 603, 1), add=1),
+    dict(id="hint2_f32_remap_add", pick=4, M=1200, N=516, K=640, hint=2, epi=F32, remap=(600, 612, 1), add=1),
+    dict(id="hint2_f32_wrap_acc1_maxo", pick=4, M=1100, N=516, K=384, hint=2, epi=F32, acc=1, maxo=1, a_wrap=192),
+    dict(id="hint2_f32_remap_wrap", pick=4, M=1200, N=516, K=640, hint=2, epi=F32, a_wrap=320, remap=(600, 604, 0)),
+    dict(id="hint2_qkv", pick=4, M=2 * 700, N=3 * 256, K=256, hint=2, epi=QKV, B=2, heads=4),
+    dict(id="hint2_conv_zero_f16", pick=4, amode=1, M=0, N=320, K=576, Cin=64, H=20, W=27, B=2, pad=4, hint=2, act=LRELU),
+    dict(id="hint2_conv_zero_f32_acc1_out2", pick=4, amode=1, M=0, N=320, K=576, Cin=64, H=20, W=27, B=2, pad=4, hint=2, epi=F32, acc=1, out2=1, act2=LRELU),
+    dict(id="hint2_conv_zero_f32_acc2_out2", pick=4, amode=1, M=0, N=320, K=576, Cin=64, H=20, W=27, B=2, pad=4, hint=2, epi=F32, acc=2, out2=1),
+    dict(id="hint2_d2s_k2", pick=4, epi=D2S, M=0, N=4 * 192, K=128, k=2, B=2, Hin=20, Win=27, pad=4, hint=2, out2=1, act2=LRELU),
+    dict(id="hint2_d2s_k4_co20", pick=4, epi=D2S, M=0, N=16 * 20, K=128, k=4, B=2, Hin=20, Win=27, pad=4, hint=2, out2=1, act2=LRELU),
+    dict(id="lnfold_consumer_hint2", pick=20, M=1100, N=528, K=256, hint=2, act=GELU, lnin=1),
+    # row-balanced schedule (N % 256 == 0, at least two 64-row units per workgroup): split-fp16 A, convolutions, QKV, the LayerNorm fold
+    dict(id="hint8_f16_wrap", pick=8, M=11000, N=1024, K=384, hint=8, act=GELU, a_wrap=192),
+    dict(id="hint8_f32_wrap_acc1", pick=8, M=11000, N=1024, K=384, hint=8, epi=F32, acc=1, a_wrap=192),
+    dict(id="hint8_f32_wrap_add", pick=8, M=11000, N=1024, K=384, hint=8, epi=F32, a_wrap=192, add=1),
+    dict(id="hint8_qkv", pick=8, M=2 * 5460, N=3 * 256, K=256, hint=8, epi=QKV, B=2, heads=4),
+    dict(id="hint8_qkv_wrap", pick=8, M=2 * 5460, N=3 * 256, K=384, hint=8, epi=QKV, B=2, heads=4, a_wrap=192),
+    dict(id="hint8_conv_zero_f16", pick=8, amode=1, M=0, N=1024, K=576, Cin=64, H=59, W=70, B=2, pad=4, hint=8, act=LRELU),
+    dict(id="hint8_conv_zero_f32_acc1_out2", pick=8, amode=1, M=0, N=1024, K=576, Cin=64, H=59, W=70, B=2, pad=4, hint=8, epi=F32, acc=1, out2=1, act2=LRELU),
+    dict(id="hint8_conv_zero_f32_acc2_out2", pick=8, amode=1, M=0, N=1024, K=576, Cin=64, H=59, W=70, B=2, pad=4, hint=8, epi=F32, acc=2, out2=1),
+    dict(id="hint8_conv_zero_f32_wrap", pick=8, amode=1, M=0, N=1024, K=1728, Cin=192, H=59, W=70, B=2, pad=4, hint=8, epi=F32, a_wrap=128),
+    dict(id="lnfold_consumer_hint8", pick=24, M=11000, N=1024, K=256, hint=8, act=GELU, lnin=1),
+    dict(id="lnfold_consumer_hint8_wrap", pick=24, M=11000, N=1024, K=384, hint=8, act=GELU, a_wrap=192, lnin=1),
+    dict(id="lnfold_consumer_hint8_qkv", pick=24, M=2 * 5460, N=3 * 256, K=256, hint=8, epi=QKV, B=2, heads=4, lnin=1),
+    # large-tile K split and the grouped problem as one tile list, fp32 epilogue (ViT-L at batch 4 / 8 / 32)
+    dict(id="hint10_f32_acc1", pick=10, M=3000, N=1024, K=2048, hint=10, epi=F32, acc=1, splitk=2),
+    dict(id="grouped_as_one_f32", pick=36, M=2816, N=1024, K=1024, epi=F32, groups=4),
 ]
 
 
@@ -495,19 +551,20 @@ def run_gemm(ops, c, lay, seed=0):
     torch.cuda.synchronize()
     # ---- checks
     tag = f"{c['id']} {lay}"
+    worst = 0.0
     for kind, name, *a in checks:
         if kind == "same":
             assert torch.equal(_bits(a[0]), _bits(a[1])), f"{tag}: {name}"
         elif kind == "vt":
             vt, vc, want, wmag = a
-            lg.assert_elementwise(vt[..., vc].reshape(-1, vc.numel()), want.reshape(-1, vc.numel()), wmag.reshape(-1, vc.numel()), K, fp16_out=True,
-                                  gelu=s["act"] == GELU, name=f"{tag} {name}")
+            worst = max(worst, lg.assert_elementwise(vt[..., vc].reshape(-1, vc.numel()), want.reshape(-1, vc.numel()), wmag.reshape(-1, vc.numel()), K,
+                                                     fp16_out=True, gelu=s["act"] == GELU, name=f"{tag} {name}"))
             unused = torch.ones(vt.shape[-1], dtype=torch.bool, device=dev)
             unused[vc] = False
             assert bool((_bits(vt[..., unused]) == 0).all()), f"{tag}: V^T columns outside the key map must stay zero"
         elif kind == "head":
             ov, o, omag, atol, r_mag = a
-            lg.assert_elementwise(ov, o, omag, K, r_mag=r_mag, atol=atol, name=f"{tag} {name}")
+            worst = max(worst, lg.assert_elementwise(ov, o, omag, K, r_mag=r_mag, atol=atol, name=f"{tag} {name}"))
         elif kind == "max":
             gm, mo_init, go = a
             assert torch.equal(_bits(gm.view), _bits(torch.maximum(mo_init, go.view))), f"{tag}: {name}"
@@ -516,7 +573,7 @@ def run_gemm(ops, c, lay, seed=0):
             x = go.view[orow].double().view(M, -1, 64)
             want = torch.stack([x.sum(-1), (x * x).sum(-1)], -1).view(M, -1)
             wmag = torch.stack([x.abs().sum(-1), (x * x).sum(-1)], -1).view(M, -1)
-            lg.assert_elementwise(grs.view, want, wmag, 64, name=f"{tag} {name}")
+            worst = max(worst, lg.assert_elementwise(grs.view, want, wmag, 64, name=f"{tag} {name}"))
         elif kind == "rsf":
             grf, go = a
             x = go.view[orow].double()
@@ -524,10 +581,11 @@ def run_gemm(ops, c, lay, seed=0):
             rstd = 1.0 / torch.sqrt(var + 1e-6)
             want = torch.stack([rstd, -mean * rstd], 1)
             wmag = torch.stack([rstd, (x.abs().mean(1) + x.std(1)) * rstd], 1)
-            lg.assert_elementwise(grf.view, want, wmag, N * N, name=f"{tag} {name}")
+            worst = max(worst, lg.assert_elementwise(grf.view, want, wmag, N * N, name=f"{tag} {name}"))
         else:
             view, rows, ref, mg, f16, gelu = a
-            lg.assert_elementwise(view[rows], ref, mg, K, fp16_out=f16, gelu=gelu, tile=tile, name=f"{tag} {name}")
+            worst = max(worst, lg.assert_elementwise(view[rows], ref, mg, K, fp16_out=f16, gelu=gelu, tile=tile, name=f"{tag} {name}"))
+    print(f"RATIO gemm {c['id']} {'strided' if lay != (0, 0) else 'dense'}{lay} {worst:.4f}")          # the worst error / bound over the case's outputs
     for i, g in enumerate(gs):
         g.check_guards(f"{c['id']} {lay} output {i}")
     return [g.written() if not hasattr(g, "cmp") else g.cmp() for g in gs]

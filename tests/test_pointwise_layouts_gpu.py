@@ -1114,6 +1114,9 @@ for _id, _kw in (("lds_C128", dict(B=2, H=11, W=19, C=128)), ("lds_C768", dict(B
 _case("dwconv7", "y16_stats", _dw_class(192, 0, 1, 0), B=2, H=11, W=19, C=192, y=0, y16=1, eps=1e-6)
 _case("dwconv7", "y16_stats_final", _dw_class(192, 0, 1, 1), B=2, H=13, W=21, C=192, y=0, y16=1, final=1, eps=1e-6)     # the plan: (115 x 154, C 192, tickets)
 _case("dwconv7", "y_y16_stats_final", _dw_class(256, 1, 1, 1), B=1, H=9, W=17, C=256, y=1, y16=1, final=1, eps=1e-6)
+# the batched V1 ConvNeXt-L plans (batch 2 at 200 x 360: C 384; batch 16 at 480 x 640: C 384 and 768): 6 / 12 channel blocks draw a pixel tile's tickets
+_case("dwconv7", "y16_stats_final_C384", _dw_class(384, 0, 1, 1), B=2, H=9, W=17, C=384, y=0, y16=1, final=1, eps=1e-6)
+_case("dwconv7", "y16_stats_final_C768", _dw_class(768, 0, 1, 1), B=1, H=9, W=17, C=768, y=0, y16=1, final=1, eps=1e-6)
 
 
 # ======================================================================================================================================
@@ -1437,6 +1440,7 @@ OPS["ray_embed"] = Op(_re_make, _re_eval, _re_bounds, _re_run, dense=True, store
 _case("ray_embed", "C256", (256,), nb=2, Hn=42, Wn=56, h=3, w=4, C=256, eps=1e-5)  # the plans: 462 x 616 -> 33 x 44, C 256 / 512, rows_per_img hw + 4
 _case("ray_embed", "C512", (512,), nb=1, Hn=70, Wn=98, h=5, w=7, C=512, eps=1e-5)
 _case("ray_embed", "C100", (100,), nb=2, Hn=28, Wn=28, h=4, w=4, C=100, eps=1e-5)
+_case("ray_embed", "C384", (384,), nb=2, Hn=42, Wn=56, h=3, w=4, C=384, eps=1e-5)   # the ViT-B/14 plans: 518 x 518 -> 37 x 37, C 384 / 768 / ...
 # the inputs cannot lower the variance of sine bands (~0.5): eps raised to variance / 100 instead, so that eps matters as it does on a low-variance row
 _case("ray_embed", "C256_eps", (256,), nb=2, Hn=42, Wn=56, h=3, w=4, C=256, eps=5e-3)
 
