@@ -35,6 +35,13 @@ GELU_SLOPE = 1.13          # max |d GELU / dx|: an accumulation error behind the
 GUARD_ROWS = 256
 
 
+def vt_cols(n):
+    """Column of key t in the V^T layout of ud_attention_f16 (include/unidepth_hip.h): the 4-key blocks of every aligned 16-key group in
+    the order [0, 2, 1, 3].  A host tensor; the permutation is its own inverse."""
+    t = torch.arange(n)
+    return (t & ~15) | ((t & 4) << 1) | ((t & 8) >> 1) | (t & 3)
+
+
 def _bits(dtype, pattern):
     return pattern          # every pattern above is positive as a signed integer of its width
 

@@ -291,6 +291,25 @@ LINEAR_F32_FLAGS = {(ldx_pad, ldc_pad, add) for ldx_pad in (False, True) for ldc
 LAYERNORM_FLAGS = {(ldx_pad, ldy_pad, remap, cls, f32, add) for ldx_pad, ldy_pad in ((False, False), (True, True)) for remap in (False, True)
                    for cls, f32, add in ((False, False, False), (True, False, False), (False, True, False), (False, False, True))}
 ATTENTION_FLAGS = None        # set below from ATT_CASES
+ATTENTION_SCHEDULES = None    # set below from ATT_CASES and the case table of tests/test_attention_paths_gpu.py
+
+
+def _attention_schedule(B, H, Nq, Nk, pre):
+    """What the attention kernels' control flow depends on besides the strides.  The pipelined kernel (pre-scaled Q): ("pipe", the steady
+    two-tile loop is taken, rem = the 1 .. 3 tiles after it, the last tile has a key tail, walk = more items per XCD than its 64 persistent
+    workgroups, fewer (image, head) pairs than XCDs).  The one-tile kernel (raw Q): ("tile", one tile only, key tail)."""
+    nt, tail = (Nk + 63) // 64, Nk % 64 != 0
+    if not pre:
+        return ("tile", nt == 1, tail)
+    t = 0
+    while t + 4 <= nt:
+        t += 2
+    pairs, qt = B * H, (Nq + 127) // 128
+    return ("pipe", t > 0, nt - t, tail, (pairs + 7) // 8 * qt > 64, pairs < 8)
+
+
+def attention_schedule(d):
+    return _attention_schedule(d.B, d.H, d.Nq, d.Nk, bool(d.q_prescaled))
 
 
 def linear_flags(d):
@@ -776,3 +795,7 @@ def test_preprocess_patches_leaves_pad_columns_untouched(ops):
 
 
 ATTENTION_FLAGS = {attention_case_flags(c) for c in ATT_CASES}
+_spec = importlib.util.spec_from_file_location("test_attention_paths_gpu", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_attention_paths_gpu.py"))
+att_paths = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(att_paths)
+ATTENTION_SCHEDULES = {_attention_schedule(c["B"], c["H"], c["Nq"], c["Nk"], bool(c["pre"])) for c in ATT_CASES + att_paths.CASES}

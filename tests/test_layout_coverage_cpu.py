@@ -96,6 +96,7 @@ def _classes(seen):
     out = dict(count={name: len(calls) for name, calls in seen.items()}, gemm={lay.gemm_class(d) for d in seen["gemm"]})
     for op, flags in _FLAGS.items():
         out[op] = {getattr(lay, flags)(d) for d in seen[op]}
+    out["attention_schedule"] = {lay.attention_schedule(d) for d in seen["attention"]}
     out["point"] = {name: {pw.point_class(name, d if isinstance(d, tuple) else (d,)) for d in calls}
                     for name, calls in seen.items() if name not in pw.ELSEWHERE}
     return out
@@ -155,6 +156,35 @@ def test_every_product_descriptor_stride_class_is_covered(recorded, op, flags, t
             missing[plan] = sorted(seen[op] - declared)
     assert not missing, (op, missing)
     assert sum(seen["count"][op] for seen in recorded.values()) > 0, op
+
+
+def test_every_product_attention_schedule_has_a_guarded_gpu_case(recorded):
+    """Every attention descriptor of the recorded plans falls into a schedule class (lay.attention_schedule: kernel, steady loop, the tiles
+    after it, key tail, persistent walk, fewer pairs than XCDs) that a case of ATT_CASES or of tests/test_attention_paths_gpu.py runs."""
+    missing = {plan: sorted(seen["attention_schedule"] - lay.ATTENTION_SCHEDULES, key=str) for plan, seen in recorded.items()
+               if seen["attention_schedule"] - lay.ATTENTION_SCHEDULES}
+    assert not missing, missing
+    assert all(seen["attention_schedule"] for seen in recorded.values())
+
+
+def test_attention_schedule_branches_no_plan_needs_are_declared_too():
+    """The tile-count branches of attention_pipe_kernel that no randn case of the suite ran before tests/test_attention_paths_gpu.py: each is
+    named here, so dropping the group of cases that reaches it fails this test by name."""
+    have = lay.ATTENTION_SCHEDULES
+    want = {"one tile with a tail (nt == 1 && tail)": ("pipe", False, 1, True, False, True),
+            "rem == 3 without the steady loop (nt = 3)": ("pipe", False, 3, True, False, True),
+            "nt = 6: the steady loop twice, rem 2": ("pipe", True, 2, True, False, True),
+            "nt = 7: the steady loop twice, rem 3": ("pipe", True, 3, True, False, True),
+            "a single-tile item with a successor": ("pipe", False, 1, True, True, False),
+            "fewer pairs than XCDs, no tail": ("pipe", False, 1, False, False, True),
+            "one-tile kernel, one tile with a tail": ("tile", True, True),
+            "one-tile kernel, several tiles, no tail": ("tile", False, False)}
+    missing = sorted(name for name, cls in want.items() if cls not in have)
+    assert not missing, missing
+    nts = {(c["pre"], -(-c["Nk"] // 64), c["Nk"] % 64 != 0) for c in lay.att_paths.CASES if c["B"] * c["H"] < 8}
+    assert {(pre, nt, tail) for pre in (0, 1) for nt in range(1, 8) for tail in (False, True)} <= nts      # the class does not tell nt = 6 from 4
+    walks = [lay._attention_schedule(c["B"], c["H"], c["Nq"], c["Nk"], True)[4] for c in lay.att_paths.CASES if c["group"] == "d"]
+    assert walks and all(walks)                                                                            # the persistent-walk cases walk
 
 
 def test_every_entry_point_is_intercepted(recorded):
