@@ -513,6 +513,45 @@ typedef struct UdEvalDepth {
 int ud_eval_depth(const UdEvalDepth* desc, void* stream);
 long long ud_eval_depth_work_bytes(int B, int H, int W);
 
+/* ---- output side: the valid pixels of a batch of predictions as packed point-cloud rows (csrc/pointcloud.hip) ----
+ * The device form of the reference's get_pointcloud_from_rgbd (unidepth/utils/visualization.py:57-104: numpy, one image per call) for a
+ * whole batch: an ordered, deterministic stream compaction in a few plain launches on `stream` (flag + count, scan, pack), no atomics,
+ * no float reduction, no workgroup waiting on another, no host synchronisation.
+ *   inputs, all device, contiguous:  points fp32 [B,3,H,W] and / or depth fp32 [B,H,W] (at least one); K fp32 [nK,3,3], nK = 1 (shared)
+ *     or B, needed when points is NULL; image u8 [B,3,H,W] or image_f32 fp32 [B,3,H,W] (at most one; both NULL = no colour);
+ *     mask u8 [B,H,W] or NULL; confidence fp32 [B,H,W] or NULL.
+ *   Predicate, all compares in fp32; d = depth[b,y,x] when depth is given, else points[b,2,y,x].  A pixel is kept when all hold:
+ *     mask == NULL || mask[b,y,x] != 0
+ *     points[b,0..2,y,x] all finite when points is given, else d finite
+ *     UD_PC_MINCONF:  confidence[b,y,x] >= min_conf                       (NaN fails)
+ *     UD_PC_RANGE:    d >= dmin && d <= dmax
+ *     UD_PC_EDGE:     fabsf(d - dn) <= edge_rtol * fminf(d, dn) for every in-image 4-neighbour dn of the same depth source (neighbours
+ *                     outside the image are skipped; a NaN or inf neighbour makes the compare false, so the pixel is dropped; the
+ *                     neighbour's own mask is not consulted)
+ *   Coordinates:  points given: points[b,:,y,x] copied bit-exactly.  Otherwise (depth mode), with fx, fy, cx, cy = K[.][0][0], [1][1],
+ *     [0][2], [1][2] of K[b] (K[0] when nK = 1; skew is ignored, as in the reference) and every operation rounded to fp32 separately:
+ *     x = ((float)u - cx) * d / fx,  y = ((float)v - cy) * d / fy,  z = d.  UD_PC_FLIP_Y negates y in either mode (the reference's +y up).
+ *   Order: images in batch order, pixels row-major inside an image (numpy boolean indexing).  Bitwise reproducible.
+ *   outputs:  counts int64 [B] = kept pixels per image and offsets int64 [B+1] = their exclusive prefix (offsets[B] = the total) are always
+ *     written, with the TRUE totals whatever `capacity` is.  xyz == NULL: count only, nothing else is written.  Otherwise, for the rows
+ *     r < min(total, capacity): xyz fp32 [capacity,3]; rgb [capacity,3] u8 (image) or fp32 (image_f32), not written without a colour
+ *     input; index int32 [capacity] = y*W+x inside the image, or NULL.  Rows r >= capacity are dropped, rows r >= total never written.
+ *   work: device scratch of at least ud_pointcloud_work_bytes(B, H, W) bytes (host-only query; one bit per pixel rounded up to tiles of
+ *     1024, plus two int32 per tile), 8-byte aligned, work_bytes its size.  Its contents need no initialisation.
+ *   Limits: 1 <= B <= 65535, H, W >= 1, H*W < 2^31 (B*H*W < 2^31 when index is given), capacity >= 0. */
+enum { UD_PC_MINCONF = 1, UD_PC_RANGE = 2, UD_PC_EDGE = 4, UD_PC_FLIP_Y = 8 };
+typedef struct UdPointCloud {
+  const float* points; const float* depth; const float* K;
+  const unsigned char* image; const float* image_f32; const unsigned char* mask; const float* confidence;
+  float* xyz; void* rgb; int* index; long long* counts; long long* offsets;
+  void* work; long long work_bytes;
+  long long capacity;
+  int B, H, W, nK, flags;
+  float min_conf, dmin, dmax, edge_rtol;
+} UdPointCloud;
+int ud_pointcloud_pack(const UdPointCloud* desc, void* stream);
+long long ud_pointcloud_work_bytes(int B, int H, int W);
+
 /* ---- launch programs: a recorded list of the ops above replayed with one call (host-side runtime) ---- */
 typedef struct UdProgram UdProgram;
 UdProgram* ud_program_create(void);
@@ -553,7 +592,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 /* the same for v_mfma_f32_16x16x32_f16 (the GEMM family's instruction): workgroups of 8 waves, sink >= workgroups * 512 floats (round 6) */
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
-/* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14) */
+/* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15) */
 int ud_version(void);
 int ud_struct_size(int which);
 const char* ud_last_error(void);

@@ -7,7 +7,8 @@ All device arithmetic runs in libunidepth_hip.so (hand-written HIP); importing t
 built library raises ImportError -- there is no CPU / eager-PyTorch fallback."""
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
 
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth"]
+_POINTCLOUD = ("PointCloud", "pack_points", "from_prediction", "get_pointcloud_from_rgbd", "save_ply", "save_file_ply")
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD]
 
 
 def __getattr__(name):
@@ -17,4 +18,7 @@ def __getattr__(name):
     if name in ("UniDepthV1", "UniDepth"):            # hubconf-style entry point / the V1 family (ConvNeXt-L / ViT-L)
         from . import hub
         return getattr(hub, name)
+    if name in _POINTCLOUD:                           # packed point clouds from infer() outputs (pointcloud.py, csrc/pointcloud.hip)
+        from . import pointcloud
+        return getattr(pointcloud, name)
     raise AttributeError(name)

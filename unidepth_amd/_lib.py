@@ -95,6 +95,16 @@ class UdEvalDepth(C.Structure):
                 ("work_bytes", i64)]
 
 
+UD_PC_MINCONF, UD_PC_RANGE, UD_PC_EDGE, UD_PC_FLIP_Y = 1, 2, 4, 8
+
+
+class UdPointCloud(C.Structure):
+    _fields_ = [("points", vp), ("depth", vp), ("K", vp), ("image", vp), ("image_f32", vp), ("mask", vp), ("confidence", vp),
+                ("xyz", vp), ("rgb", vp), ("index", vp), ("counts", vp), ("offsets", vp), ("work", vp), ("work_bytes", i64),
+                ("capacity", i64), ("B", i32), ("H", i32), ("W", i32), ("nK", i32), ("flags", i32),
+                ("min_conf", f32), ("dmin", f32), ("dmax", f32), ("edge_rtol", f32)]
+
+
 (UD_V1_RESIZE_AA, UD_V1_SH_EMBED, UD_V1_SOFTMAX, UD_V1_ATTN_FEWQ, UD_V1_HEAD_MIX) = range(1, 6)
 (UD_V1_ADD, UD_V1_COPY_ROWS) = (8, 9)
 (UD_V1_CAMERA, UD_V1_POINTS, UD_V1_MEAN3, UD_V1_PREPROCESS, UD_V1_VIT_TAP) = range(11, 16)
@@ -203,6 +213,7 @@ def _load():
         "ud_knn_split": [P(UdKnn)],
         "ud_extract_patches": [P(UdExtractPatches), vp],
         "ud_eval_depth": [P(UdEvalDepth), vp],
+        "ud_pointcloud_pack": [P(UdPointCloud), vp],
         "ud_program_run": [vp, i32, i32, vp],
         "ud_calib_mfma_stream": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
         "ud_calib_mfma_stream16": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
@@ -219,7 +230,9 @@ def _load():
     lib.ud_last_error.restype = C.c_char_p
     lib.ud_eval_depth_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_eval_depth_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth]):
+    lib.ud_pointcloud_work_bytes.argtypes = [i32, i32, i32]
+    lib.ud_pointcloud_work_bytes.restype = i64
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud]):
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)
         if lib.ud_struct_size(i) != C.sizeof(st):

@@ -21,6 +21,9 @@ done
 ( hipcc $FLAGS -ffp-contract=off "$@" -c evalops.hip -o $BD/evalops.o ) & pids+=($!)
 # 2-D depth metrics: the resample weights, ratios and rescales must round every operation separately (threshold counts), same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c evaldepth.hip -o $BD/evaldepth.o ) & pids+=($!)
+# point-cloud compaction: the filter predicate and the unprojection round every operation separately (a numpy fp32 restatement
+# reproduces the predicate exactly), same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c pointcloud.hip -o $BD/pointcloud.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)
