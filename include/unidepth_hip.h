@@ -552,6 +552,41 @@ typedef struct UdPointCloud {
 int ud_pointcloud_pack(const UdPointCloud* desc, void* stream);
 long long ud_pointcloud_work_bytes(int B, int H, int W);
 
+/* ---- validation side: network-resolution maps brought to the ground truth's size (csrc/matchgt.hip) ----
+ * The device form of the reference's match_gt / match_intrinsics (unidepth/utils/misc.py:596-690: per image, slice the padded window,
+ * F.interpolate(bilinear, align_corners=False) to the target window, F.pad with zeros, torch.cat -- once per map) for a whole batch
+ * whose images carry DIFFERENT paddings: ONE launch on `stream`, no atomics, no workspace, no host synchronisation, bitwise reproducible.
+ *   Geometry, shared by every plane: source maps are h1 x w1, destinations H2 x W2.  pads1 / pads2: device int32 [B,4] in (left, right,
+ *     top, bottom) order, or NULL for zeros.  Image b reads the source window [pt : h1-pb, pl : w1-pr] (hu x wu) and writes the
+ *     destination window [p2t : H2-p2b, p2l : W2-p2r] (h2 x w2); destination pixels outside it are written as 0.  The kernel clamps the
+ *     paddings so that hu, wu >= 1 and h2, w2 >= 0 and every source index stays inside [0, h1) x [0, w1) whatever the arrays hold
+ *     (callers validate on the host; an empty destination window gives an all-zero image).
+ *   planes[0 .. n_planes): src fp32 [B or 1, C, h1, w1] contiguous per image, image b at src + b * src_batch_stride floats (0 broadcasts
+ *     one source, e.g. the rays of a single ground-truth camera); mul: optional fp32 [B,1,h1,w1] multiplied into every tap before
+ *     blending (points = rays * radius without the product at network resolution); dst fp32 [B,C,H2,W2] contiguous, 4-byte aligned.
+ *   Arithmetic along each axis, for window-relative destination index o of n2 from n source samples (fp32, every operation rounded
+ *     separately; the same as ud_eval_depth's resample): s = (float)n / (float)n2, f = max(s * ((float)o + 0.5f) - 0.5f, 0),
+ *     i0 = min((int)f, n-1), i1 = i0 + (i0 < n-1), l = clamp(f - (float)i0, 0, 1), h = 1 - l;
+ *     out = (v00 * hx + v01 * lx) * hy + (v10 * hx + v11 * lx) * ly, every v = src (* mul, rounded) at (y0|y1, x0|x1).
+ *     hu == h2 && wu == w2: a bit copy of the window (of the rounded product when mul is given).
+ *   Intrinsics (optional, both or neither): K_in, K_out fp32 [B,3,3] (may alias).  With sx = (float)((double)w2 / (double)wu), sy likewise:
+ *     fx' = fx * sx, fy' = fy * sy, cx' = (cx - pl) * sx + p2l, cy' = (cy - pt) * sy + p2t, every operation rounded separately; the other
+ *     seven entries are copied.  n_planes = 0 with K given runs the intrinsics alone.
+ *   Limits: 1 <= B <= 65535, h1, w1, H2, W2 >= 1, C >= 1, C * H2 < 2^31, n_planes <= UD_MATCH_MAX_PLANES; offsets are 64-bit. */
+#define UD_MATCH_MAX_PLANES 4
+typedef struct UdMatchPlane {
+  const float* src; const float* mul; float* dst;
+  int C;
+  long long src_batch_stride;
+} UdMatchPlane;
+typedef struct UdMatchGt {
+  UdMatchPlane planes[UD_MATCH_MAX_PLANES];
+  const int* pads1; const int* pads2;
+  const float* K_in; float* K_out;
+  int n_planes, B, h1, w1, H2, W2;
+} UdMatchGt;
+int ud_match_gt(const UdMatchGt* desc, void* stream);
+
 /* ---- launch programs: a recorded list of the ops above replayed with one call (host-side runtime) ---- */
 typedef struct UdProgram UdProgram;
 UdProgram* ud_program_create(void);
@@ -592,7 +627,8 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 /* the same for v_mfma_f32_16x16x32_f16 (the GEMM family's instruction): workgroups of 8 waves, sink >= workgroups * 512 floats (round 6) */
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
-/* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15) */
+/* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17;
+ * 16 is not assigned and answers -1 like every unknown index) */
 int ud_version(void);
 int ud_struct_size(int which);
 const char* ud_last_error(void);

@@ -8,7 +8,8 @@ built library raises ImportError -- there is no CPU / eager-PyTorch fallback."""
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
 
 _POINTCLOUD = ("PointCloud", "pack_points", "from_prediction", "get_pointcloud_from_rgbd", "save_ply", "save_file_ply")
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD]
+_MATCHING = ("match_gt", "match_intrinsics")
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING]
 
 
 def __getattr__(name):
@@ -21,4 +22,7 @@ def __getattr__(name):
     if name in _POINTCLOUD:                           # packed point clouds from infer() outputs (pointcloud.py, csrc/pointcloud.hip)
         from . import pointcloud
         return getattr(pointcloud, name)
+    if name in _MATCHING:                             # outputs matched to the ground truth (matching.py, csrc/matchgt.hip)
+        from . import matching
+        return getattr(matching, name)
     raise AttributeError(name)

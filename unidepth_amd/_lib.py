@@ -105,6 +105,18 @@ class UdPointCloud(C.Structure):
                 ("min_conf", f32), ("dmin", f32), ("dmax", f32), ("edge_rtol", f32)]
 
 
+UD_MATCH_MAX_PLANES = 4
+
+
+class UdMatchPlane(C.Structure):
+    _fields_ = [("src", vp), ("mul", vp), ("dst", vp), ("C", i32), ("src_batch_stride", i64)]
+
+
+class UdMatchGt(C.Structure):
+    _fields_ = [("planes", UdMatchPlane * UD_MATCH_MAX_PLANES), ("pads1", vp), ("pads2", vp), ("K_in", vp), ("K_out", vp),
+                ("n_planes", i32), ("B", i32), ("h1", i32), ("w1", i32), ("H2", i32), ("W2", i32)]
+
+
 (UD_V1_RESIZE_AA, UD_V1_SH_EMBED, UD_V1_SOFTMAX, UD_V1_ATTN_FEWQ, UD_V1_HEAD_MIX) = range(1, 6)
 (UD_V1_ADD, UD_V1_COPY_ROWS) = (8, 9)
 (UD_V1_CAMERA, UD_V1_POINTS, UD_V1_MEAN3, UD_V1_PREPROCESS, UD_V1_VIT_TAP) = range(11, 16)
@@ -214,6 +226,7 @@ def _load():
         "ud_extract_patches": [P(UdExtractPatches), vp],
         "ud_eval_depth": [P(UdEvalDepth), vp],
         "ud_pointcloud_pack": [P(UdPointCloud), vp],
+        "ud_match_gt": [P(UdMatchGt), vp],
         "ud_program_run": [vp, i32, i32, vp],
         "ud_calib_mfma_stream": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
         "ud_calib_mfma_stream16": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
@@ -232,7 +245,9 @@ def _load():
     lib.ud_eval_depth_work_bytes.restype = i64
     lib.ud_pointcloud_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_pointcloud_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud]):
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt]):
+        if st is None:                                  # index 16 is not assigned: the library answers -1
+            continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)
         if lib.ud_struct_size(i) != C.sizeof(st):

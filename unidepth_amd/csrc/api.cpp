@@ -10,7 +10,7 @@ void ud_set_error(const char* msg) {
 }
 
 extern "C" const char* ud_last_error(void) { return g_err; }
-extern "C" int ud_version(void) { return 112; }
+extern "C" int ud_version(void) { return 113; }
 
 // struct sizes, so the Python binding can verify its ctypes mirror of include/unidepth_hip.h
 extern "C" int ud_struct_size(int which) {
@@ -31,6 +31,7 @@ extern "C" int ud_struct_size(int which) {
     case 13: return (int)sizeof(UdCameraHead);
     case 14: return (int)sizeof(UdEvalDepth);
     case 15: return (int)sizeof(UdPointCloud);
+    case 17: return (int)sizeof(UdMatchGt);     // 16 stays unassigned (-1)
     default: return -1;
   }
 }

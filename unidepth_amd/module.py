@@ -7,7 +7,7 @@ The engine holds its weights as repacked device buffers behind the C-ABI, not as
 meaning instead of an AttributeError:
 
 * `isinstance(model, torch.nn.Module)` holds; `parameters()` / `buffers()` are empty (nothing is trainable here: inference engine);
-* `model(...)` = `forward(...)` = `infer(...)`;
+* `model(...)` = `forward(...)` = `infer(...)`; with a dict first argument (`model(inputs, image_metas)`) it is `forward_test(...)`;
 * `.half() / .float() / .double() / .bfloat16() / .to(dtype)` are no-ops with a warning: operand precision is part of the kernels
   (fp16 MFMA operands, fp32 statistics and residual streams), not a property of stored tensors;
 * `.train()` raises for `mode=True` (there is no backward), `.eval()` / `.train(False)` return self, `requires_grad_()` is a no-op;
@@ -31,6 +31,11 @@ except Exception:                                       # pragma: no cover - hug
     class _HubMixin:                                    # type: ignore[no-redef]
         def __init_subclass__(cls, **kwargs):
             super().__init_subclass__()
+
+
+def _is_batch_dict(args, kwargs) -> bool:
+    """The reference's validation call `model(batch["data"], batch["img_metas"])`: a dict where infer() takes the image tensor."""
+    return isinstance(args[0] if args else kwargs.get("inputs"), dict)
 
 
 class EngineModule(torch.nn.Module, _HubMixin):
@@ -114,7 +119,10 @@ class EngineModule(torch.nn.Module, _HubMixin):
 
     # ---- call path -------------------------------------------------------------------------------------------------------
     def forward(self, *args, **kwargs):
-        """`model(rgb, camera)` runs infer(): the reference's training-time forward(inputs, image_metas) has no counterpart here."""
+        """`model(rgb, camera)` runs infer(); `model(inputs, image_metas)` with a dict first argument is the reference's eval-mode
+        forward(inputs, image_metas) = forward_test (its training-time forward has no counterpart here)."""
+        if _is_batch_dict(args, kwargs):
+            return self.forward_test(*args, **kwargs)
         return self.infer(*args, **kwargs)
 
     # ---- weights (HF mixin layout: config.json + model.safetensors / pytorch_model.bin) -----------------------------------

@@ -630,6 +630,12 @@ class UniDepthV1(EngineModule):
 
     __call__ = infer
 
+    def forward_test(self, inputs, image_metas=None, **kwargs):
+        """The reference's validation forward (unidepthv1.py forward_test).  Not available: UniDepthV1 has no network-resolution plan
+        here (its launch program starts from the input image); UniDepthV2.forward_test is the implemented one."""
+        raise NotImplementedError("UniDepthV1.forward_test: not implemented -- UniDepthV1 has no network-resolution plan on this engine; "
+                                  "use infer() per image, or UniDepthV2.forward_test")
+
     @torch.no_grad()
     def infer_with_taps(self, rgbs: torch.Tensor, intrinsics=None, skip_camera: bool = False):
         """infer() + the decoder's intermediate tensors (segmented replay of the launch program; parity tooling)."""

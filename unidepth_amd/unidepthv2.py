@@ -26,7 +26,7 @@ from .ops import (UD_A_CONV3_REFLECT, UD_A_CONV3_REFLECT_UP, UD_A_CONV3_ZERO, UD
 from .cameras import GT_OPENCV, GT_PINHOLE, BatchCamera, as_camera
 
 GT_GIVEN_RAYS = 15          # plan tag: the ray map itself is supplied (pixel_decoder seam, decoder.py:400 `rays_gt`)
-from .module import EngineModule
+from .module import EngineModule, _is_batch_dict
 from .plan import PlanRecorder
 from .weights import _rup, arch_of, pack
 
@@ -510,6 +510,24 @@ class UniDepthV2(EngineModule):
         if self.interpolation_mode not in ("bilinear", "bicubic"):
             raise ValueError(f"interpolation_mode {self.interpolation_mode!r}: 'bilinear' or 'bicubic' (align_corners=False) expected")
         self._ensure_packed()
+        with torch.cuda.device(self._device):
+            plan, B, order = self._run_plan(rgb, camera, normalize, slot, taps)
+            out = self._collect(plan, B)
+            if order is not None:
+                ui = self._unsort(order)
+                out = {k: (v.index_select(0, ui) if v.shape[0] == B else v) for k, v in out.items()}
+            return out
+
+    def _unsort(self, order):
+        """Index tensor that puts a batch processed in `order` (mixed cameras: sorted by model) back in the caller's order."""
+        unsort = torch.empty(len(order), dtype=torch.long)
+        unsort[torch.tensor(order)] = torch.arange(len(order))
+        return unsort.to(self._device)
+
+    def _run_plan(self, rgb, camera, normalize, slot, taps, net=False):
+        """The shared front of infer() and forward_test(): camera bookkeeping, plan lookup, input upload, program replay.  net: `rgb` is
+        the network image itself (normalised, multiples of 14; no padding, no resize).  Returns (plan, B, order): order is None, or the
+        permutation the images were processed in (BatchCamera of mixed models).  Call under torch.cuda.device(self._device)."""
         if rgb.ndim == 3:
             rgb = rgb.unsqueeze(0)
         B, _, H, W = rgb.shape
@@ -527,53 +545,49 @@ class UniDepthV2(EngineModule):
             if Kc is not None:
                 assert Kc.shape[-1] == 3 and Kc.shape[-2] == 3, "camera tensor should be of shape (..., 3, 3): assume pinhole"
                 Kc = Kc.detach().reshape(-1, 3, 3).float().cpu()
-        is_u8 = rgb.dtype == torch.uint8
-        with torch.cuda.device(self._device):
-            cam_nb = 0 if camera is None else (Kc.shape[0] if Kc is not None else cam_obj.params.shape[0])
-            # one camera broadcasts over the batch, otherwise one per image (the reference fails with a shape error here too)
-            assert cam_nb in (0, 1, B), f"camera batch {cam_nb} does not match the image batch {B} (one camera, or one per image)"
-            gt_mode = 0 if camera is None else (GT_PINHOLE if Kc is not None else cam_obj.gt_mode)
-            mixed = isinstance(cam_obj, BatchCamera)               # one camera per image, models differ (or are iterative): one ray launch per image
-            unsort = None
-            if mixed:
-                assert cam_nb == B, f"BatchCamera of {cam_nb} cameras for a batch of {B} images (one per image)"
-                # canonical order: images sorted by camera model (stable), so a plan (2.6 GB at bs = 8, keyed on the tuple of per-image models)
-                # is shared by every ORDERING of the same models instead of being rebuilt per ordering; infer() is bit-exactly
-                # batch-permutation equivariant, the outputs are put back in the caller's order below
-                modes = cam_obj.gt_modes
-                order = sorted(range(B), key=lambda i: modes[i])
-                if order != list(range(B)):
-                    idx = torch.tensor(order, device=rgb.device)
-                    rgb = rgb.index_select(0, idx)
-                    cam_obj = BatchCamera([cam_obj.cameras[i] for i in order])
-                    unsort = torch.empty(B, dtype=torch.long)
-                    unsort[torch.tensor(order)] = torch.arange(B)
-                gt_mode = cam_obj.gt_modes
-            self._check_camera_head()
-            plan = self._plan(B, H, W, cam_nb, is_u8, bool(normalize), int(slot), gt_mode)
-            plan.rgb.copy_(rgb if is_u8 else rgb.float(), non_blocking=True)
-            if mixed:
-                buf = torch.zeros(B, 16)
-                for i, c in enumerate(cam_obj.cameras):
-                    if c.gt_mode == GT_PINHOLE:                    # K^-1 in the first nine slots
-                        buf[i, :9] = self._network_kinv(plan, c.K).reshape(9)
-                    else:
-                        pn = c.network_params(plan.paddings, plan.rf)
-                        buf[i, : pn.shape[1]] = pn[0]
-                plan.kinv_gt.copy_(buf)
-            elif cam_obj is not None:
-                pn = cam_obj.network_params(plan.paddings, plan.rf)               # [n, <= 16] -> the parameter slots of the ray kernel
-                buf = torch.zeros(pn.shape[0], plan.kinv_gt.shape[1])
-                buf[:, :pn.shape[1]] = pn
-                plan.kinv_gt.copy_(buf)
-            if Kc is not None:
-                plan.kinv_gt.copy_(self._network_kinv(plan, Kc).reshape(-1, 9))
-            self._run(plan, 0, len(plan.prog), taps)
-            out = self._collect(plan, B)
-            if unsort is not None:
-                ui = unsort.to(self._device)
-                out = {k: (v.index_select(0, ui) if v.shape[0] == B else v) for k, v in out.items()}
-            return out
+        is_u8 = rgb.dtype == torch.uint8 and not net
+        if net:
+            normalize = False
+        cam_nb = 0 if camera is None else (Kc.shape[0] if Kc is not None else cam_obj.params.shape[0])
+        # one camera broadcasts over the batch, otherwise one per image (the reference fails with a shape error here too)
+        assert cam_nb in (0, 1, B), f"camera batch {cam_nb} does not match the image batch {B} (one camera, or one per image)"
+        gt_mode = 0 if camera is None else (GT_PINHOLE if Kc is not None else cam_obj.gt_mode)
+        mixed = isinstance(cam_obj, BatchCamera)               # one camera per image, models differ (or are iterative): one ray launch per image
+        sorted_order = None
+        if mixed:
+            assert cam_nb == B, f"BatchCamera of {cam_nb} cameras for a batch of {B} images (one per image)"
+            # canonical order: images sorted by camera model (stable), so a plan (2.6 GB at bs = 8, keyed on the tuple of per-image models)
+            # is shared by every ORDERING of the same models instead of being rebuilt per ordering; infer() is bit-exactly
+            # batch-permutation equivariant, the outputs are put back in the caller's order below
+            modes = cam_obj.gt_modes
+            order = sorted(range(B), key=lambda i: modes[i])
+            if order != list(range(B)):
+                idx = torch.tensor(order, device=rgb.device)
+                rgb = rgb.index_select(0, idx)
+                cam_obj = BatchCamera([cam_obj.cameras[i] for i in order])
+                sorted_order = order
+            gt_mode = cam_obj.gt_modes
+        self._check_camera_head()
+        plan = self._plan(B, H, W, cam_nb, is_u8, bool(normalize), int(slot), gt_mode, net)
+        plan.rgb.copy_(rgb if is_u8 else rgb.float(), non_blocking=True)
+        if mixed:
+            buf = torch.zeros(B, 16)
+            for i, c in enumerate(cam_obj.cameras):
+                if c.gt_mode == GT_PINHOLE:                    # K^-1 in the first nine slots
+                    buf[i, :9] = self._network_kinv(plan, c.K).reshape(9)
+                else:
+                    pn = c.network_params(plan.paddings, plan.rf)
+                    buf[i, : pn.shape[1]] = pn[0]
+            plan.kinv_gt.copy_(buf)
+        elif cam_obj is not None:
+            pn = cam_obj.network_params(plan.paddings, plan.rf)               # [n, <= 16] -> the parameter slots of the ray kernel
+            buf = torch.zeros(pn.shape[0], plan.kinv_gt.shape[1])
+            buf[:, :pn.shape[1]] = pn
+            plan.kinv_gt.copy_(buf)
+        if Kc is not None:
+            plan.kinv_gt.copy_(self._network_kinv(plan, Kc).reshape(-1, 9))
+        self._run(plan, 0, len(plan.prog), taps)
+        return plan, B, sorted_order
 
     @staticmethod
     def _network_kinv(plan: _Plan, K: torch.Tensor) -> torch.Tensor:
@@ -631,7 +645,66 @@ class UniDepthV2(EngineModule):
         out["depth_features"] = plan.depth_features.clone()
         return {k: out[k] for k in ("confidence", "intrinsics", "radius", "depth", "points", "rays", "depth_features")}
 
-    __call__ = infer
+    @torch.no_grad()
+    def forward_test(self, inputs: dict, image_metas=None, *, slot: int = 0):
+        """The reference's validation forward (unidepthv2.py:134-160 forward_test over :341-379 encode_decode), what its validate() loop
+        reaches through `model(batch["data"], batch["img_metas"])`:
+          inputs["image"]  [B,3,Hn,Wn] float, the dataset's already normalised network-resolution image (Hn, Wn multiples of 14);
+          inputs["depth"]  [B,1,H2,W2] ground truth -- only its shape is used;
+          paddings of the image inside the network frame: image_metas[i]["paddings"] = (left, top, right, bottom), reordered to
+          (left, right, top, bottom) as the reference does (:345-351), otherwise inputs["paddings"] [B,4] already in that order;
+          missing = zeros;  inputs.get("camera"): ground-truth camera(s) of the network image -- a [...,3,3] pinhole tensor, a
+          cameras.* object or a reference-class object -- whose rays replace the predicted ones (no crop, no resize).
+        The network-resolution launch program runs end to end (not through the pixel_encoder / pixel_decoder seams), then ONE ud_match_gt
+        crops every image's padding, resamples to the ground truth's size and rescales the intrinsics (matching.py).  Returns the
+        reference's five keys: depth [B,1,H2,W2], points [B,3,H2,W2], confidence [B,1,H2,W2], intrinsics [B,3,3] and rays [B,3,Hn,Wn].
+        rays stay at NETWORK resolution: the reference overwrites its matched rays with the network rays divided by their norm clipped at
+        1e-5 (:147-152), kept here.  `inputs` is not modified.  `slot` as in infer()."""
+        from . import matching
+        if not isinstance(inputs, dict) or "image" not in inputs or "depth" not in inputs:
+            raise ValueError("forward_test: inputs must be a dict with 'image' [B,3,Hn,Wn] and 'depth' [B,1,H2,W2]")
+        image, depth_gt = inputs["image"], inputs["depth"]
+        if not isinstance(image, torch.Tensor) or image.ndim != 4 or image.shape[1] != 3 or not image.is_floating_point():
+            raise ValueError(f"forward_test: inputs['image'] must be a float [B,3,Hn,Wn] tensor, got {tuple(getattr(image, 'shape', ()))}")
+        B, _, Hn, Wn = image.shape
+        if B < 1 or Hn < 14 or Wn < 14 or Hn % 14 or Wn % 14:
+            raise ValueError(f"forward_test: network image {Hn} x {Wn}: H and W must be multiples of the patch size (14)")
+        if not isinstance(depth_gt, torch.Tensor) or depth_gt.ndim != 4 or depth_gt.shape[0] != B or min(depth_gt.shape[-2:]) < 1:
+            raise ValueError(f"forward_test: inputs['depth'] must be [B,1,H2,W2] with B = {B}, got {tuple(getattr(depth_gt, 'shape', ()))}")
+        H2, W2 = (int(v) for v in depth_gt.shape[-2:])
+        pads = inputs.get("paddings", None)
+        if image_metas is not None and len(image_metas) and "paddings" in image_metas[0]:
+            pads = [[m["paddings"][i] for i in (0, 2, 1, 3)] for m in image_metas]            # ltrb -> lrtb
+        p1 = matching.host_paddings(pads, B, Hn, Wn, "forward_test: paddings")
+        self._ensure_packed()
+        dev, f32 = self._device, torch.float32
+        with torch.cuda.device(dev):
+            plan, _, order = self._run_plan(image, inputs.get("camera", None), False, slot, None, net=True)
+            if order is not None and p1 is not None:
+                p1 = [p1[i] for i in order]
+            npx = Hn * Wn
+            ray_stride = 0 if plan.nb == 1 else 3 * npx                                     # one ground-truth camera broadcasts
+            out = {"depth": torch.empty(B, 1, H2, W2, dtype=f32, device=dev), "points": torch.empty(B, 3, H2, W2, dtype=f32, device=dev),
+                   "confidence": torch.empty(B, 1, H2, W2, dtype=f32, device=dev), "intrinsics": torch.empty(B, 3, 3, dtype=f32, device=dev)}
+            d1, _ = matching.upload_paddings(p1, None, dev)
+            # points = rays * radius and depth = its z are formed tap by tap inside the resample: no product at network resolution
+            matching.launch([dict(src=plan.rays, mul=plan.net[0], dst=out["points"], C=3, src_batch_stride=ray_stride),
+                             dict(src=plan.rays.data_ptr() + 2 * npx * 4, mul=plan.net[0], dst=out["depth"], C=1, src_batch_stride=ray_stride),
+                             dict(src=plan.net[1], dst=out["confidence"], C=1, src_batch_stride=npx)],
+                            B, Hn, Wn, H2, W2, d1, None, plan.K33, out["intrinsics"])
+            rays = plan.rays / torch.norm(plan.rays, dim=1, keepdim=True).clip(min=1e-5)
+            out["rays"] = rays.expand(B, 3, Hn, Wn)
+            if order is not None:
+                ui = self._unsort(order)
+                out = {k: v.index_select(0, ui) for k, v in out.items()}
+            return {k: out[k] for k in ("depth", "points", "confidence", "rays", "intrinsics")}
+
+    def __call__(self, *args, **kwargs):
+        """model(rgb, camera, ...) is infer(); model(inputs, image_metas) with a dict first argument is forward_test() -- the reference's
+        eval-mode forward (unidepthv2.py:162-166)."""
+        if _is_batch_dict(args, kwargs):
+            return self.forward_test(*args, **kwargs)
+        return self.infer(*args, **kwargs)
 
     # ---- module seams (SURVEY.md 8b/B2): the two halves of encode_decode() (unidepthv2.py:341-379) with the reference's signatures,
     # each a sub-range of the launch program of a network-resolution plan, so either half can be swapped for the reference's /
