@@ -587,6 +587,54 @@ typedef struct UdMatchGt {
 } UdMatchGt;
 int ud_match_gt(const UdMatchGt* desc, void* stream);
 
+/* ---- output side: maps of a batch rendered as colour images, a grid of panels per image (csrc/colorize.hip) ----
+ * The device form of the reference's colorize (unidepth/utils/visualization.py:17-36: numpy + matplotlib, one image per call) and of
+ * its image_grid of equal-sized panels (scripts/demo.py: rgb | gt / pred | error), for a whole batch in at most two launches on `stream`
+ * (a partial min / max pass only when a panel is auto-ranged, then the render pass): no atomics, no host synchronisation, bitwise
+ * reproducible.
+ *   dst u8 [B, rows*H, cols*W, 3], or [B, 3, rows*H, cols*W] with UD_CZ_CHW; contiguous, any alignment.  Cell (r, c) is
+ *   panels[r * cols + c] and covers dst rows [r*H, (r+1)*H) and columns [c*W, (c+1)*W); rows * cols <= UD_COLORIZE_MAX_PANELS.
+ *   Panel kinds (all sources device, contiguous per image; image b at src + b * batch_stride ELEMENTS, so a map may be a channel of a
+ *   larger tensor, e.g. depth = points[:, 2]; 0 broadcasts one image):
+ *     UD_CZ_NONE  the cell is not written: its bytes keep their bits.
+ *     UD_CZ_MAP   src fp32 [H, W]: v = src[y, x].
+ *     UD_CZ_AREL  src = g, src2 = p, both fp32 [H, W] (batch_stride2 for p): v = g == 0 ? 0 : fabsf(g - p) / g, every operation rounded
+ *                 separately (the demo's error map), then coloured like a map.
+ *     UD_CZ_RGB   src u8 [3, H, W] copied through (interleaved for the HWC destination).
+ *   Colour of a map value v with the panel's lut u8 [256, 3] (device), in fp32 with IEEE division, every operation rounded separately:
+ *     t = (v - lo) / den;  x = t * 256.0f;
+ *     x is NaN -> (0,0,0);  x < 0 -> lut[0];  x >= 256 -> lut[255];  otherwise lut[(int)x];  finally v < 1e-4f -> (0,0,0) (false for a NaN).
+ *   Range of a panel: without auto flags lo and den are the descriptor's (the host passes lo = (float)vmin and
+ *     den = (float)((double)vmax - (double)vmin), numpy's promotion of Python floats against a float32 array; hi is ignored).
+ *     UD_CZ_AUTO_LO takes lo = the image's minimum, UD_CZ_AUTO_HI takes hi = its maximum, each over ALL pixels of image b of this panel
+ *     (invalid ones included) and NaN if any pixel is NaN, as ndarray.min() / max(); the other limit is the descriptor's lo / hi; then
+ *     den = hi - lo rounded in fp32.  The range is per image and per panel.  Flags of an rgb panel are ignored.
+ *   work: device scratch of at least ud_colorize_work_bytes(B, H, W) bytes (host-only query: three floats per panel slot and chunk of
+ *     1024 pixels), 4-byte aligned, work_bytes its size; needed only when a panel is auto-ranged (NULL otherwise).  No initialisation.
+ *   Limits: 1 <= B <= 65535, H, W >= 1, H*W < 2^31, 3*cols*W < 2^31, rows, cols >= 1, rows*cols <= 4, batch strides >= 0, fp32 sources
+ *     4-byte aligned; offsets are 64-bit.  The render pass covers a cell with tiles of 4 rows x 256 pixels laid from the 4-byte boundary
+ *     at or before a row's first byte, ceil(H / 4) * ceil((W + 3) / 256) of them, and one launch takes at most UD_COLORIZE_MAX_TILES
+ *     (its x extent in threads stays below 2^32): this binds only below W = 32, where an image may be 2^26 - 4 rows tall.
+ *     ud_colorize_work_bytes answers -1 for sizes beyond these.  Every refusal is returned before any HIP call. */
+#define UD_COLORIZE_MAX_PANELS 4
+#define UD_COLORIZE_MAX_TILES 0xffffff
+enum { UD_CZ_NONE = 0, UD_CZ_MAP = 1, UD_CZ_AREL = 2, UD_CZ_RGB = 3 };
+enum { UD_CZ_AUTO_LO = 1, UD_CZ_AUTO_HI = 2 };        /* UdColorPanel.flags */
+enum { UD_CZ_CHW = 1 };                               /* UdColorize.flags */
+typedef struct UdColorPanel {
+  const void* src; const float* src2; const unsigned char* lut;
+  long long batch_stride, batch_stride2;
+  int kind, flags;
+  float lo, hi, den;
+} UdColorPanel;
+typedef struct UdColorize {
+  UdColorPanel panels[UD_COLORIZE_MAX_PANELS];
+  unsigned char* dst; void* work; long long work_bytes;
+  int B, H, W, rows, cols, flags;
+} UdColorize;
+int ud_colorize(const UdColorize* desc, void* stream);
+long long ud_colorize_work_bytes(int B, int H, int W);
+
 /* ---- launch programs: a recorded list of the ops above replayed with one call (host-side runtime) ---- */
 typedef struct UdProgram UdProgram;
 UdProgram* ud_program_create(void);
@@ -627,8 +675,8 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 /* the same for v_mfma_f32_16x16x32_f16 (the GEMM family's instruction): workgroups of 8 waves, sink >= workgroups * 512 floats (round 6) */
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
-/* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17;
- * 16 is not assigned and answers -1 like every unknown index) */
+/* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
+ * UdColorize = 18; 16 is not assigned and answers -1 like every unknown index) */
 int ud_version(void);
 int ud_struct_size(int which);
 const char* ud_last_error(void);

@@ -9,7 +9,8 @@ from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
 
 _POINTCLOUD = ("PointCloud", "pack_points", "from_prediction", "get_pointcloud_from_rgbd", "save_ply", "save_file_ply")
 _MATCHING = ("match_gt", "match_intrinsics")
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING]
+_VISUALIZATION = ("colorize", "colorize_batch", "demo_panel", "image_grid", "save_png", "preload_colormap")
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION]
 
 
 def __getattr__(name):
@@ -25,4 +26,7 @@ def __getattr__(name):
     if name in _MATCHING:                             # outputs matched to the ground truth (matching.py, csrc/matchgt.hip)
         from . import matching
         return getattr(matching, name)
+    if name in _VISUALIZATION:                        # depth maps as colour images (visualization.py, csrc/colorize.hip)
+        from . import visualization
+        return getattr(visualization, name)
     raise AttributeError(name)

@@ -117,6 +117,22 @@ class UdMatchGt(C.Structure):
                 ("n_planes", i32), ("B", i32), ("h1", i32), ("w1", i32), ("H2", i32), ("W2", i32)]
 
 
+UD_COLORIZE_MAX_PANELS = 4
+UD_CZ_NONE, UD_CZ_MAP, UD_CZ_AREL, UD_CZ_RGB = 0, 1, 2, 3
+UD_CZ_AUTO_LO, UD_CZ_AUTO_HI = 1, 2
+UD_CZ_CHW = 1
+
+
+class UdColorPanel(C.Structure):
+    _fields_ = [("src", vp), ("src2", vp), ("lut", vp), ("batch_stride", i64), ("batch_stride2", i64), ("kind", i32), ("flags", i32),
+                ("lo", f32), ("hi", f32), ("den", f32)]
+
+
+class UdColorize(C.Structure):
+    _fields_ = [("panels", UdColorPanel * UD_COLORIZE_MAX_PANELS), ("dst", vp), ("work", vp), ("work_bytes", i64),
+                ("B", i32), ("H", i32), ("W", i32), ("rows", i32), ("cols", i32), ("flags", i32)]
+
+
 (UD_V1_RESIZE_AA, UD_V1_SH_EMBED, UD_V1_SOFTMAX, UD_V1_ATTN_FEWQ, UD_V1_HEAD_MIX) = range(1, 6)
 (UD_V1_ADD, UD_V1_COPY_ROWS) = (8, 9)
 (UD_V1_CAMERA, UD_V1_POINTS, UD_V1_MEAN3, UD_V1_PREPROCESS, UD_V1_VIT_TAP) = range(11, 16)
@@ -227,6 +243,7 @@ def _load():
         "ud_eval_depth": [P(UdEvalDepth), vp],
         "ud_pointcloud_pack": [P(UdPointCloud), vp],
         "ud_match_gt": [P(UdMatchGt), vp],
+        "ud_colorize": [P(UdColorize), vp],
         "ud_program_run": [vp, i32, i32, vp],
         "ud_calib_mfma_stream": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
         "ud_calib_mfma_stream16": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
@@ -245,7 +262,9 @@ def _load():
     lib.ud_eval_depth_work_bytes.restype = i64
     lib.ud_pointcloud_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_pointcloud_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt]):
+    lib.ud_colorize_work_bytes.argtypes = [i32, i32, i32]
+    lib.ud_colorize_work_bytes.restype = i64
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize]):
         if st is None:                                  # index 16 is not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:

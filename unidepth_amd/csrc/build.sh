@@ -26,6 +26,8 @@ done
 ( hipcc $FLAGS -ffp-contract=off "$@" -c pointcloud.hip -o $BD/pointcloud.o ) & pids+=($!)
 # match_gt: the resample of ud_eval_depth applied to per-image windows; bit-exact against its numpy fp32 restatement, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c matchgt.hip -o $BD/matchgt.o ) & pids+=($!)
+# colorize: (v - lo) / den * 256 picks a LUT bin and |g - p| / g feeds it; byte-exact against its numpy fp32 restatement, same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c colorize.hip -o $BD/colorize.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)
