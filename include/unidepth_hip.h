@@ -635,6 +635,64 @@ typedef struct UdColorize {
 int ud_colorize(const UdColorize* desc, void* stream);
 long long ud_colorize_work_bytes(int B, int H, int W);
 
+/* ---- output side: the point clouds of a batch splatted into depth maps (csrc/splat.hip) ----
+ * The device form of the reference's project_points (unidepth/utils/geometric.py:161-204: a per-image loop of scatter_add_, the mean depth
+ * per pixel) and the z-buffer a re-rendered view needs (nearest surface wins), for a whole batch in three plain launches on `stream`
+ * (fill the work words, splat one thread per point, resolve one thread per pixel): integer atomics only, no float atomics, no workgroup
+ * waiting on another, no host synchronisation.  Bitwise reproducible: the result does not depend on the order the points arrive in.
+ *   Sources, all device fp32.  Strided form (offsets == NULL): image b has n_points points; coordinate c of point r is at
+ *     xyz[b * batch_stride + r * point_stride + c * comp_stride] (ELEMENTS): planar [B,3,h,w] is (3hw, 1, hw), rows [B,N,3] are (3N, 3, 1);
+ *     batch_stride = 0 splats one cloud into every image.  Packed form (offsets != NULL: device int64 [B+1], e.g. UdPointCloud's): n_points
+ *     is the number of rows behind xyz, row i is at xyz[i * point_stride + c * comp_stride] (batch_stride is ignored), image b owns the
+ *     rows [offsets[b], min(offsets[b+1], n_points)) and r = i - offsets[b]; the kernel finds a row's image by a search over the offsets,
+ *     which are never read on the host; rows owned by no image are skipped.  comp_stride = 1 rows are read with one 12-byte load.
+ *   Arithmetic per point, fp32, every operation rounded separately, left to right:
+ *     T fp32 [nT,3,4] (nT = 1 or B; NULL = none), t = T[b] (T[0] when nT = 1):  x' = ((t00*x + t01*y) + t02*z) + t03, y' and z' likewise
+ *       from rows 1 and 2.  Without T: x' = x, y' = y, z' = z.
+ *     K fp32 [nK,3,3] (nK = 1 or B; the FULL matrix, as the reference's matmul):  a = (k00*x' + k01*y') + k02*z', b_ and w likewise from
+ *       rows 1 and 2;  u = a / w + pixel_offset,  v = b_ / w + pixel_offset  (IEEE division).
+ *     Cell: fu = floorf(u), or truncf(u) with UD_SPLAT_TRUNC (the reference's .int(): u in (-1, 0) gives -0.0f and lands in column 0, as
+ *       it does there); the column is (int)fu when fu >= 0.0f && fu < 2^31 (decided in float before converting: a NaN or an infinite u
+ *       fails, -0.0f passes) and (int)fu < W; otherwise the point is dropped.  Rows likewise from v and H.
+ *     UD_SPLAT_RANGE drops the point when !(z' >= dmin && z' <= dmax).  The depth of a point is z'.
+ *   mode UD_SPLAT_NEAREST: additionally drops !(z' > 0).  Each kept point makes one 64-bit atomicMin with the key (bits(z') << 32) | r on
+ *     its pixel: the smallest z' wins, among equal z' the smallest r.  depth = the winner's z' (its bits), 0 where nothing landed; index
+ *     int32 [B,H,W] (optional) = the winner's r, -1 for holes; rgb [B,3,H,W] (with color; u8, or fp32 with color_f32 != 0) = the winner's
+ *     colour, gathered from `color` with the SAME strides and offsets as xyz (component = channel), holes 0; count int32 [B,H,W]
+ *     (optional; costs a second atomic per point) = the number of kept points on the pixel.
+ *   mode UD_SPLAT_MEAN (the reference's semantics; z' <= 0 allowed): drops !(fabsf(z') <= 2^20); each kept point adds llrintf(z' * 2^24)
+ *     (round to nearest even; the product is exact) to the pixel's int64 sum and 1 to its uint32 count.
+ *     depth = (float)((double)sum / ((double)count * 16777216.0)), 0 where count == 0 and NaN where count >= 2^19 (the sum's headroom);
+ *     count int32 [B,H,W] is optional; index and rgb are refused.
+ *   outputs: depth fp32 [B,H,W] always; every pixel of every requested output is written, outputs not requested are not touched.
+ *   work: device scratch, 8-byte aligned, work_bytes its size: 8 B per pixel of the batch, plus 4 B per pixel when counts are kept (mean
+ *     mode, or count given).  ud_splat_work_bytes(B, H, W) (host-only) answers 12 B per pixel, enough for both, and -1 beyond the limits.
+ *     Its contents need no initialisation.
+ *   Limits: 1 <= B <= 65535, H, W >= 1, H*W < 2^31, 0 <= n_points < 2^31, point_stride, comp_stride >= 1, batch_stride >= 0; offsets are
+ *     64-bit.  Every refusal is returned before any HIP call. */
+enum { UD_SPLAT_NEAREST = 0, UD_SPLAT_MEAN = 1 };     /* UdSplat.mode */
+enum { UD_SPLAT_TRUNC = 1, UD_SPLAT_RANGE = 2 };      /* UdSplat.flags */
+typedef struct UdSplat {
+  const float* xyz; const long long* offsets; const float* K; const float* T; const void* color;
+  float* depth; int* index; void* rgb; int* count;
+  void* work; long long work_bytes;
+  long long batch_stride, point_stride, comp_stride, n_points;
+  int B, H, W, nK, nT, mode, flags, color_f32;
+  float pixel_offset, dmin, dmax;
+} UdSplat;
+int ud_splat(const UdSplat* desc, void* stream);
+long long ud_splat_work_bytes(int B, int H, int W);
+
+/* The reference's `downsample` (unidepth/utils/geometric.py:208-224), a hole-aware min-pool of sparse depth maps, in one launch:
+ * src fp32 [N,1,H,W] contiguous -> dst fp32 [N,1,H/factor,W/factor].  Every value == 0 (either sign) of a factor x factor block counts as
+ * 1e5f; the output is the block's minimum, written as 0 when it is > 1000, and NaN when the block holds a NaN (torch.min).  Exact.
+ * Limits: 1 <= N <= 65535, 1 <= factor <= 64, H and W multiples of factor, H*W < 2^31.  Every refusal is returned before any HIP call. */
+typedef struct UdDepthMinPool {
+  const float* src; float* dst;
+  int N, H, W, factor;
+} UdDepthMinPool;
+int ud_depth_minpool(const UdDepthMinPool* desc, void* stream);
+
 /* ---- launch programs: a recorded list of the ops above replayed with one call (host-side runtime) ---- */
 typedef struct UdProgram UdProgram;
 UdProgram* ud_program_create(void);
@@ -676,7 +734,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18; 16 is not assigned and answers -1 like every unknown index) */
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21; 16 and 19 are not assigned and answer -1 like every unknown index) */
 int ud_version(void);
 int ud_struct_size(int which);
 const char* ud_last_error(void);

@@ -10,7 +10,8 @@ from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
 _POINTCLOUD = ("PointCloud", "pack_points", "from_prediction", "get_pointcloud_from_rgbd", "save_ply", "save_file_ply")
 _MATCHING = ("match_gt", "match_intrinsics")
 _VISUALIZATION = ("colorize", "colorize_batch", "demo_panel", "image_grid", "save_png", "preload_colormap")
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION]
+_REPROJECT = ("RenderedView", "render_depth", "reproject", "project_points", "downsample")
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT]
 
 
 def __getattr__(name):
@@ -29,4 +30,7 @@ def __getattr__(name):
     if name in _VISUALIZATION:                        # depth maps as colour images (visualization.py, csrc/colorize.hip)
         from . import visualization
         return getattr(visualization, name)
+    if name in _REPROJECT:                            # point clouds back into depth maps (reproject.py, csrc/splat.hip)
+        import importlib                              # not `from . import reproject`: that asks this function for "reproject" first
+        return getattr(importlib.import_module(".reproject", __name__), name)
     raise AttributeError(name)

@@ -133,6 +133,21 @@ class UdColorize(C.Structure):
                 ("B", i32), ("H", i32), ("W", i32), ("rows", i32), ("cols", i32), ("flags", i32)]
 
 
+UD_SPLAT_NEAREST, UD_SPLAT_MEAN = 0, 1
+UD_SPLAT_TRUNC, UD_SPLAT_RANGE = 1, 2
+
+
+class UdSplat(C.Structure):
+    _fields_ = [("xyz", vp), ("offsets", vp), ("K", vp), ("T", vp), ("color", vp), ("depth", vp), ("index", vp), ("rgb", vp), ("count", vp),
+                ("work", vp), ("work_bytes", i64), ("batch_stride", i64), ("point_stride", i64), ("comp_stride", i64), ("n_points", i64),
+                ("B", i32), ("H", i32), ("W", i32), ("nK", i32), ("nT", i32), ("mode", i32), ("flags", i32), ("color_f32", i32),
+                ("pixel_offset", f32), ("dmin", f32), ("dmax", f32)]
+
+
+class UdDepthMinPool(C.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("N", i32), ("H", i32), ("W", i32), ("factor", i32)]
+
+
 (UD_V1_RESIZE_AA, UD_V1_SH_EMBED, UD_V1_SOFTMAX, UD_V1_ATTN_FEWQ, UD_V1_HEAD_MIX) = range(1, 6)
 (UD_V1_ADD, UD_V1_COPY_ROWS) = (8, 9)
 (UD_V1_CAMERA, UD_V1_POINTS, UD_V1_MEAN3, UD_V1_PREPROCESS, UD_V1_VIT_TAP) = range(11, 16)
@@ -244,6 +259,8 @@ def _load():
         "ud_pointcloud_pack": [P(UdPointCloud), vp],
         "ud_match_gt": [P(UdMatchGt), vp],
         "ud_colorize": [P(UdColorize), vp],
+        "ud_splat": [P(UdSplat), vp],
+        "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_program_run": [vp, i32, i32, vp],
         "ud_calib_mfma_stream": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
         "ud_calib_mfma_stream16": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
@@ -264,8 +281,10 @@ def _load():
     lib.ud_pointcloud_work_bytes.restype = i64
     lib.ud_colorize_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_colorize_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize]):
-        if st is None:                                  # index 16 is not assigned: the library answers -1
+    lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
+    lib.ud_splat_work_bytes.restype = i64
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool]):
+        if st is None:                                  # indices 16 and 19 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

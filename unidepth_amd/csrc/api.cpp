@@ -10,7 +10,7 @@ void ud_set_error(const char* msg) {
 }
 
 extern "C" const char* ud_last_error(void) { return g_err; }
-extern "C" int ud_version(void) { return 114; }
+extern "C" int ud_version(void) { return 115; }
 
 // struct sizes, so the Python binding can verify its ctypes mirror of include/unidepth_hip.h
 extern "C" int ud_struct_size(int which) {
@@ -33,6 +33,8 @@ extern "C" int ud_struct_size(int which) {
     case 15: return (int)sizeof(UdPointCloud);
     case 17: return (int)sizeof(UdMatchGt);     // 16 stays unassigned (-1)
     case 18: return (int)sizeof(UdColorize);
+    case 20: return (int)sizeof(UdSplat);        // 19 stays unassigned (-1)
+    case 21: return (int)sizeof(UdDepthMinPool);
     default: return -1;
   }
 }

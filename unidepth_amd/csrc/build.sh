@@ -28,6 +28,8 @@ done
 ( hipcc $FLAGS -ffp-contract=off "$@" -c matchgt.hip -o $BD/matchgt.o ) & pids+=($!)
 # colorize: (v - lo) / den * 256 picks a LUT bin and |g - p| / g feeds it; byte-exact against its numpy fp32 restatement, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c colorize.hip -o $BD/colorize.o ) & pids+=($!)
+# splat: the cell a point lands in (transform, projection, division, floor) must be the one a numpy fp32 restatement computes, same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c splat.hip -o $BD/splat.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)
