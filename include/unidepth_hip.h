@@ -693,6 +693,64 @@ typedef struct UdDepthMinPool {
 } UdDepthMinPool;
 int ud_depth_minpool(const UdDepthMinPool* desc, void* stream);
 
+/* ---- validation inputs: antialiased resize with crop, pad and normalise fused in (csrc/testprep.hip) ----
+ * The device form of the reference's test-time ContextCrop (unidepth/datasets/pipelines/transforms.py:1131-1355: crop / zero-pad to a
+ * window, TF.resize(BICUBIC, antialias=True) on the uint8 tensor, NEAREST on the validity mask, camera crop and resize) followed by
+ * /255 and TF.normalize, and of F.interpolate(mode, antialias=True, align_corners=False) in general: ONE launch on `stream`, no atomics,
+ * no workspace, no host synchronisation, bitwise reproducible.
+ *   src: [B,C,h,w] contiguous, uint8 (src_u8 = 1) or fp32 (any alignment of its element type).  The window (top, left, height, width)
+ *     is in source pixels and may reach outside the image (samples outside are 0, like TF.pad) or cut it.  The window is resized to a
+ *     virtual Ho x Wo image of which dst [B,C,Hn,Wn] contiguous holds the rows [dtop, dtop + Hn) and columns [dleft, dleft + Wn)
+ *     (Ho = Hn, Wo = Wn, dtop = dleft = 0 for the whole image; a destination window is a resize followed by a crop without the pixels
+ *     in between).
+ *   Weights along an axis of `in` window samples and `out` virtual destination samples (ATen's _compute_indices_min_size_weights_aa,
+ *     align_corners = False), fp32 with every operation rounded separately (the library is built without FMA contraction here):
+ *       scale = (float)in / (float)out, big = scale >= 1 ? scale : 1, support = (interp_size * 0.5f) * big (interp_size 4 bicubic, 2
+ *       bilinear), inv = scale >= 1 ? 1.0f / scale : 1, center = scale * ((float)i + 0.5f),
+ *       xmin = max((int)(center - support + 0.5f), 0), xsize = min((int)(center + support + 0.5f), in) - xmin
+ *       (then clamped: 0 <= xmin <= in - 1, 1 <= xsize <= min(in - xmin, UD_RESIZE_MAX_TAPS): no effect inside the limits below),
+ *       w_j = filter(((float)(j + xmin) - center + 0.5f) * inv), total = ((w_0 + w_1) + w_2) + ..., w_j = w_j / total.
+ *       bicubic (a = -0.5f), x = |x|:  x < 1: ((a + 2) * x - (a + 3)) * x * x + 1;  x < 2: (((x - 5) * x + 8) * x - 4) * a;  else 0.
+ *       bilinear (triangle), x = |x|:  x < 1: 1 - x;  else 0.
+ *       in == out: xmin = i, xsize = 1, w_0 = 1 (the axis is copied).
+ *   Value: the horizontal pass first, t[y][ox] = (w_0 * s[y][xmin]) + w_1 * s[y][xmin + 1] + ... (left to right, products and sums
+ *     rounded separately, s = the window's sample as fp32), then the vertical pass over t with the row weights, top to bottom, the same
+ *     way.  With both axes copied an fp32 destination is a bit copy of the window.  The result does not depend on the tiling.
+ *   out_form: UD_RESIZE_OUT_F32   dst fp32 = the value
+ *             UD_RESIZE_OUT_U8    dst uint8 = clamp(rintf(value), 0, 255) (round half to even: what torchvision's resize does to a uint8
+ *                                 tensor on a GPU -- cast to float, interpolate, round, clamp, cast)
+ *             UD_RESIZE_OUT_NORM  dst fp32 = ((float)u8 / 255.0f - mean[c]) * inv_std[c] of that byte (C <= 4): the reference's resize,
+ *                                 /255 and TF.normalize in one store
+ *   Mask plane (mask_dst != NULL): uint8 [B,1,Hn,Wn] from mask_src uint8 [B,1,h,w], or from an implied all-ones mask when mask_src is
+ *     NULL; cropped / zero-padded by the same window and resized with the NEAREST rule of F.interpolate:
+ *     src = min((int)floorf((float)(o + d) * scale), in - 1) along each axis (scale as above, d = dtop / dleft).
+ *   Intrinsics (optional, both or neither): K_in, K_out fp32 [B,3,3] (may alias).  camera.crop then camera.resize of a pinhole:
+ *     K[0][2] -= (float)left, K[1][2] -= (float)top, then the six entries of the first two rows times zoom = (float)((double)Ho /
+ *     (double)height); the third row is copied.  The destination window does not enter.
+ *   Limits: B * (C + 1) <= 65535, every size >= 1, height <= UD_RESIZE_MAX_SCALE * Ho and width <= UD_RESIZE_MAX_SCALE * Wo.  A call
+ *     beyond the scale limit is REFUSED with UD_ERR_BAD_ARG (the kernel's tiles -- staged span, intermediate rows and the weight tables in
+ *     LDS -- are bounded at compile time by UD_RESIZE_MAX_TAPS = 4 * UD_RESIZE_MAX_SCALE + 1 taps; within the bound the host sizes them
+ *     for the call's own scale factors; there is no chunked fall-back beyond it).
+ *     The kernel clamps every index, so no descriptor content makes it read or write outside its buffers. */
+#define UD_RESIZE_BICUBIC 0
+#define UD_RESIZE_BILINEAR 1
+#define UD_RESIZE_OUT_F32 0
+#define UD_RESIZE_OUT_U8 1
+#define UD_RESIZE_OUT_NORM 2
+#define UD_RESIZE_MAX_SCALE 8
+#define UD_RESIZE_MAX_TAPS 33
+typedef struct UdResizeAA {
+  const void* src; void* dst;
+  const unsigned char* mask_src; unsigned char* mask_dst;
+  const float* K_in; float* K_out;
+  int B, C, h, w;
+  int top, left, height, width;
+  int Ho, Wo, dtop, dleft, Hn, Wn;
+  int src_u8, filter, out_form;
+  float mean[4], inv_std[4];
+} UdResizeAA;
+int ud_resize_aa(const UdResizeAA* desc, void* stream);
+
 /* ---- launch programs: a recorded list of the ops above replayed with one call (host-side runtime) ---- */
 typedef struct UdProgram UdProgram;
 UdProgram* ud_program_create(void);
@@ -734,7 +792,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21; 16 and 19 are not assigned and answer -1 like every unknown index) */
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23; 16, 19 and 22 are not assigned and answer -1 like every unknown index) */
 int ud_version(void);
 int ud_struct_size(int which);
 const char* ud_last_error(void);

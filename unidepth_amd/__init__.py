@@ -11,7 +11,8 @@ _POINTCLOUD = ("PointCloud", "pack_points", "from_prediction", "get_pointcloud_f
 _MATCHING = ("match_gt", "match_intrinsics")
 _VISUALIZATION = ("colorize", "colorize_batch", "demo_panel", "image_grid", "save_png", "preload_colormap")
 _REPROJECT = ("RenderedView", "render_depth", "reproject", "project_points", "downsample")
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT]
+_TESTPREP = ("TestGeometry", "test_geometry", "prepare_test_batch", "resize_aa", "original_image")
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP]
 
 
 def __getattr__(name):
@@ -33,4 +34,7 @@ def __getattr__(name):
     if name in _REPROJECT:                            # point clouds back into depth maps (reproject.py, csrc/splat.hip)
         import importlib                              # not `from . import reproject`: that asks this function for "reproject" first
         return getattr(importlib.import_module(".reproject", __name__), name)
+    if name in _TESTPREP:                             # validation inputs from raw uint8 images (testprep.py, csrc/testprep.hip)
+        from . import testprep
+        return getattr(testprep, name)
     raise AttributeError(name)

@@ -148,6 +148,18 @@ class UdDepthMinPool(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("N", i32), ("H", i32), ("W", i32), ("factor", i32)]
 
 
+UD_RESIZE_BICUBIC, UD_RESIZE_BILINEAR = 0, 1
+UD_RESIZE_OUT_F32, UD_RESIZE_OUT_U8, UD_RESIZE_OUT_NORM = 0, 1, 2
+UD_RESIZE_MAX_SCALE, UD_RESIZE_MAX_TAPS = 8, 33
+
+
+class UdResizeAA(C.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("mask_src", vp), ("mask_dst", vp), ("K_in", vp), ("K_out", vp),
+                ("B", i32), ("C", i32), ("h", i32), ("w", i32), ("top", i32), ("left", i32), ("height", i32), ("width", i32),
+                ("Ho", i32), ("Wo", i32), ("dtop", i32), ("dleft", i32), ("Hn", i32), ("Wn", i32),
+                ("src_u8", i32), ("filter", i32), ("out_form", i32), ("mean", f32 * 4), ("inv_std", f32 * 4)]
+
+
 (UD_V1_RESIZE_AA, UD_V1_SH_EMBED, UD_V1_SOFTMAX, UD_V1_ATTN_FEWQ, UD_V1_HEAD_MIX) = range(1, 6)
 (UD_V1_ADD, UD_V1_COPY_ROWS) = (8, 9)
 (UD_V1_CAMERA, UD_V1_POINTS, UD_V1_MEAN3, UD_V1_PREPROCESS, UD_V1_VIT_TAP) = range(11, 16)
@@ -261,6 +273,7 @@ def _load():
         "ud_colorize": [P(UdColorize), vp],
         "ud_splat": [P(UdSplat), vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
+        "ud_resize_aa": [P(UdResizeAA), vp],
         "ud_program_run": [vp, i32, i32, vp],
         "ud_calib_mfma_stream": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
         "ud_calib_mfma_stream16": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
@@ -283,8 +296,8 @@ def _load():
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool]):
-        if st is None:                                  # indices 16 and 19 are not assigned: the library answers -1
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA]):
+        if st is None:                                  # indices 16, 19 and 22 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

@@ -30,6 +30,9 @@ done
 ( hipcc $FLAGS -ffp-contract=off "$@" -c colorize.hip -o $BD/colorize.o ) & pids+=($!)
 # splat: the cell a point lands in (transform, projection, division, floor) must be the one a numpy fp32 restatement computes, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c splat.hip -o $BD/splat.o ) & pids+=($!)
+# testprep: the antialiased resize's weights, both passes, the rounding to a byte and the normalisation are defined operation by
+# operation in fp32; bit-exact against its numpy fp32 restatement, same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c testprep.hip -o $BD/testprep.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)
