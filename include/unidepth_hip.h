@@ -512,6 +512,38 @@ typedef struct UdEvalDepth {
 } UdEvalDepth;
 int ud_eval_depth(const UdEvalDepth* desc, void* stream);
 long long ud_eval_depth_work_bytes(int B, int H, int W);
+/* 3-D point metrics of a batch: replaces utils/evaluation_depth.py eval_3d (:160-182: the nearest-exact resample to about 240 x 320 valid
+ * points per batch, then per image DICT_METRICS_3D = MSE_3d, chamfer, F1 on the masked points), as eight stream-ordered launches with no
+ * host synchronisation and no device-to-host copy (csrc/eval3d.hip).
+ *   gt, pred fp32 [B,3,H,W]; mask u8 [B,H,W] (nonzero = valid); thresholds fp32 [T], compared with SQUARED distances, any order.
+ *   Sample size, on the device from S = the number of valid pixels of the batch, in the reference's fp32 arithmetic:
+ *   q = 76800.0f / (float)S, r = sqrtf(q) correctly rounded; r >= 1: (h, w) = (H, W); else h = (int)((float)H * r), w = (int)((float)W * r).
+ *   gt, pred and mask are sampled on the h x w grid by F.interpolate(mode="nearest-exact")'s rule, source = min(floor((dst + 0.5f) *
+ *   ((float)in / (float)out)), in - 1); the valid samples of image b, row-major, are its n_b points (the order of gt[:, mask]).
+ *   S = 0, h = 0 or w = 0: every image is empty (size still reports the rule's (h, w); S = 0 reports (H, W)).
+ *   out fp32 [3,B], rows MSE_3d, chamfer, F1 of every image:
+ *     MSE_3d   mean over the points of the fp32 L2 norm of gt - pred;
+ *     chamfer  mean of (sqrtf(d1_i) + sqrtf(d2_i)) / 2, d1 = gt -> pred and d2 = pred -> gt the squared distances to the nearest
+ *              neighbour, bit-equal to ud_knn_points' dists on the same rows (K = 1, norm 2);
+ *     F1       c1_t = #(d1 < th_t), c2_t = #(d2 < th_t) (strict, fp32); p_t = (float)c1_t / (float)n_b, r_t = (float)c2_t / (float)n_b,
+ *              f_t = 2 p_t r_t / (p_t + r_t) in fp32 with NaN -> 0; F1 = trapz(f, dx = 1) / T (0 for T = 1);
+ *     an image with n_b = 0 gets NaN in all three rows (the reference skips it and returns fewer rows: out[:, counts > 0] is its result).
+ *   counts int64 [B] = n_b; size int32 [2] = (h, w).
+ *   work: device scratch, 16-byte aligned, of at least ud_eval_3d_work_bytes(B, H, W, T) bytes (host-only query; -1 for sizes outside the
+ *   limits), work_bytes its size.  It is sized for H * W points per image: no tighter bound is known on the host.
+ *   Limits: 1 <= B <= UD_EVAL3D_MAX_B, H, W >= 1, H * W < 2^31 - 1024, B * H * W < 2^36 (launch grids), 1 <= T <= UD_EVAL3D_MAX_T (the
+ *   thresholds and their counters sit in LDS; the reference uses 100).
+ *   Bitwise reproducible: fp64 sums reduced in a fixed order, integer atomics only. */
+#define UD_EVAL3D_MAX_B 32767
+#define UD_EVAL3D_MAX_T 1024
+typedef struct UdEval3d {
+  const float* gt; const float* pred; const unsigned char* mask; const float* thresholds;
+  float* out; long long* counts; int* size;
+  void* work; long long work_bytes;
+  int B, H, W, T;
+} UdEval3d;
+int ud_eval_3d(const UdEval3d* desc, void* stream);
+long long ud_eval_3d_work_bytes(int B, int H, int W, int T);
 
 /* ---- output side: the valid pixels of a batch of predictions as packed point-cloud rows (csrc/pointcloud.hip) ----
  * The device form of the reference's get_pointcloud_from_rgbd (unidepth/utils/visualization.py:57-104: numpy, one image per call) for a
@@ -792,7 +824,8 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23; 16, 19 and 22 are not assigned and answer -1 like every unknown index) */
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25; 16, 19, 22 and 24 are not assigned and answer -1 like every unknown
+ * index) */
 int ud_version(void);
 int ud_struct_size(int which);
 const char* ud_last_error(void);

@@ -95,6 +95,14 @@ class UdEvalDepth(C.Structure):
                 ("work_bytes", i64)]
 
 
+UD_EVAL3D_MAX_B, UD_EVAL3D_MAX_T = 32767, 1024
+
+
+class UdEval3d(C.Structure):
+    _fields_ = [("gt", vp), ("pred", vp), ("mask", vp), ("thresholds", vp), ("out", vp), ("counts", vp), ("size", vp),
+                ("work", vp), ("work_bytes", i64), ("B", i32), ("H", i32), ("W", i32), ("T", i32)]
+
+
 UD_PC_MINCONF, UD_PC_RANGE, UD_PC_EDGE, UD_PC_FLIP_Y = 1, 2, 4, 8
 
 
@@ -268,6 +276,7 @@ def _load():
         "ud_knn_split": [P(UdKnn)],
         "ud_extract_patches": [P(UdExtractPatches), vp],
         "ud_eval_depth": [P(UdEvalDepth), vp],
+        "ud_eval_3d": [P(UdEval3d), vp],
         "ud_pointcloud_pack": [P(UdPointCloud), vp],
         "ud_match_gt": [P(UdMatchGt), vp],
         "ud_colorize": [P(UdColorize), vp],
@@ -290,14 +299,16 @@ def _load():
     lib.ud_last_error.restype = C.c_char_p
     lib.ud_eval_depth_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_eval_depth_work_bytes.restype = i64
+    lib.ud_eval_3d_work_bytes.argtypes = [i32, i32, i32, i32]
+    lib.ud_eval_3d_work_bytes.restype = i64
     lib.ud_pointcloud_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_pointcloud_work_bytes.restype = i64
     lib.ud_colorize_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA]):
-        if st is None:                                  # indices 16, 19 and 22 are not assigned: the library answers -1
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d]):
+        if st is None:                                  # indices 16, 19, 22 and 24 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

@@ -33,6 +33,9 @@ done
 # testprep: the antialiased resize's weights, both passes, the rounding to a byte and the normalisation are defined operation by
 # operation in fp32; bit-exact against its numpy fp32 restatement, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c testprep.hip -o $BD/testprep.o ) & pids+=($!)
+# eval_3d: |gt - pred| and the nearest-neighbour distances (knn_dist.h, shared with evalops.hip) round every multiply and add
+# separately, so the distances are bit-equal to ud_knn_points' and a numpy fp32 restatement reproduces the threshold counts, same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c eval3d.hip -o $BD/eval3d.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)

@@ -19,13 +19,12 @@
 // partial winners meet in a 64-bit atomicMin on (dist bits << 32 | j) -- distances are >= 0, so the integer order IS the
 // lexicographic (dist, j) order.
 #include "ud_common.h"
+#include "knn_dist.h"
 
 namespace {
 
 // built with -ffp-contract=off (csrc/build.sh): the distance sums below must round the multiply and the add separately
 #pragma clang fp contract(off)
-
-constexpr int KNN_TILE = 1024;
 
 template <int DC>
 struct KnnTile {                       // floats per staged point
@@ -150,14 +149,7 @@ __global__ __launch_bounds__(256) void knn_kernel(const UdKnn p, const int span)
 // packed ops per 2 pairs), and the running minimum is kept WITHOUT its index (one v_min3_f32 per query per two points); the index is
 // recovered only for the rare 8-point chunk whose minimum beats the best so far, by re-running that chunk with the strict-<
 // update (same instructions, so bit-identical distances; first minimum still wins).  ~5.4 issue slots per pair instead of 11.
-constexpr int KNN1_CHUNK = 8;
-
-__device__ __forceinline__ f32x2 knn1_dist(const f32x2 qx, const f32x2 qy, const f32x2 qz, const f32x4 v, const bool l2) {
-  const f32x2 dx = qx - (f32x2){v[0], v[0]}, dy = qy - (f32x2){v[1], v[1]}, dz = qz - (f32x2){v[2], v[2]};
-  if (l2) return (dx * dx + dy * dy) + dz * dz;
-  return ((f32x2){fabsf(dx[0]), fabsf(dx[1])} + (f32x2){fabsf(dy[0]), fabsf(dy[1])}) + (f32x2){fabsf(dz[0]), fabsf(dz[1])};
-}
-
+// KNN_TILE, KNN1_CHUNK and knn1_dist (the per-pair arithmetic) live in knn_dist.h, shared with eval3d.hip.
 template <bool L2>
 __global__ __launch_bounds__(256) void knn1_d3_kernel(const UdKnn p, const int span) {
   __shared__ f32x4 tile[KNN_TILE];

@@ -4,6 +4,8 @@
     ChamferDistance, chamfer_dist   unidepth/utils/chamfer_distance.py:60-159, unidepth/utils/evaluation_depth.py:12-18
     auc, f1_score, DICT_METRICS_3D, eval_3d   unidepth/utils/evaluation_depth.py:21-34,74-91,109-125,160-182 (the 3-D metrics)
     eval_depth, DICT_METRICS, DICT_METRICS_D  unidepth/utils/evaluation_depth.py:37-72,93-110,124-147 (the 2-D depth metrics)
+    eval_3d_batch, eval_3d_size, thresholds_3d  eval_3d of a whole batch in one ud_eval_3d call (csrc/eval3d.hip), no host synchronisation
+    MetricsAccumulator              datasets/base_dataset.py:219-271 (metrics_store / metrics_count / get_evaluation, one process)
     RandomPatchExtractor            unidepth/ops/extract_patches/modules/patch_extractor.py:10-42 (forward)
 
 Same names, argument meaning and error behaviour; inference / evaluation only (no autograd: the reference's backward kernels are
@@ -11,9 +13,11 @@ training code).  Tensors must live on the GPU: there is no CPU path.  eval_depth
 dtype (the reference computes in the input dtype), and run in ud_eval_depth without any host synchronisation."""
 from __future__ import annotations
 
+import math
 from collections import namedtuple
 from typing import Optional, Tuple, Union
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -287,3 +291,137 @@ DICT_METRICS_D = {           # utils/evaluation_depth.py:124-129: per-pixel maps
     "a1": lambda gt, pred: (torch.maximum((gt / pred), (pred / gt)) > 1.25 ** 1.0).to(torch.float32),
     "abs_rel": lambda gt, pred: (torch.abs(gt - pred) / gt),
 }
+
+
+# ---- 3-D metrics of a batch on the device (utils/evaluation_depth.py eval_3d; datasets/base_dataset.py accumulate_metrics_3d) -----------
+
+EVAL_3D_KEYS = ("MSE_3d", "chamfer", "F1")                                # the reference's dict order = the rows of ud_eval_3d's out
+
+
+def eval_3d_size(H: int, W: int, n_valid: int) -> Tuple[int, int]:
+    """The size (h, w) eval_3d resamples [.., H, W] maps to when the batch has n_valid valid pixels, in the reference's arithmetic:
+    ratio = min(1.0, (240 * 320 / masks.sum()) ** 0.5) is an fp32 tensor there, so the quotient, the square root and the products
+    H * ratio, W * ratio are fp32 and int() truncates them.  Pure host code (numpy float32); ud_eval_3d computes the same on the
+    device.  n_valid = 0 gives (H, W): every image is empty anyway."""
+    if n_valid <= 0:
+        return int(H), int(W)
+    q = np.float32(76800.0) / np.float32(n_valid)
+    r = np.float32(np.sqrt(np.float64(q)))             # through fp64 and back: the correctly rounded fp32 square root
+    if r >= np.float32(1.0):
+        return int(H), int(W)
+    return int(np.float32(H) * r), int(np.float32(W) * r)
+
+
+def thresholds_3d(min_depth: float, max_depth: float, device=None) -> torch.Tensor:
+    """The 100 F1 thresholds of accumulate_metrics_3d (datasets/base_dataset.py): linspace(log(min_depth), log(max_depth / 20), 100).exp(),
+    fp32, made by torch on `device` as the reference makes them."""
+    return torch.linspace(math.log(min_depth), math.log(max_depth / 20), 100, device=device).exp()
+
+
+def eval_3d_batch(gts: torch.Tensor, preds: torch.Tensor, masks: torch.Tensor, thresholds):
+    """eval_3d (utils/evaluation_depth.py:160-182) for a whole batch in one ud_eval_3d call: gts, preds [B,3,H,W], masks [B,1,H,W] or
+    [B,H,W] (bool, or any dtype with nonzero = valid), thresholds a list of floats or a tensor [T] (converted to fp32 once, compared
+    with SQUARED distances as in the reference, any order).  Returns {"MSE_3d", "chamfer", "F1"}, each fp32 [B], plus "count" int64 [B]
+    (the points of every image after the resample) and "size" int32 [2] (the resample size (h, w) = eval_3d_size(H, W, masks.sum())).
+    Every tensor stays on the GPU and nothing synchronises: the valid count, the size, the nearest-exact resample, the compaction, the
+    two nearest-neighbour searches per image (each direction once) and the metrics are eight stream-ordered launches.  Bitwise
+    reproducible.
+
+    An image without a valid sample has count 0 and NaN in the three rows.  The reference's eval_3d skips such images and so returns
+    fewer rows: out[name][out["count"] > 0] is what it returns.  The size follows the reference's fp32 rule; eval_ops.eval_3d above
+    multiplies in fp64 and is one pixel smaller for some sizes (518 x 518 x 3 fully valid: 159 instead of 160).  Inputs of another
+    float dtype are converted to fp32 and non-contiguous views are made contiguous first."""
+    for name, t in (("gts", gts), ("preds", preds)):
+        if not isinstance(t, torch.Tensor) or t.ndim != 4 or t.shape[1] != 3:
+            raise ValueError(f"eval_3d_batch: {name} must be [B,3,H,W], got {tuple(getattr(t, 'shape', ()))}")
+        if not t.is_floating_point():
+            raise ValueError(f"eval_3d_batch: {name} must be a float tensor, got {t.dtype}")
+    if preds.shape != gts.shape:
+        raise ValueError(f"eval_3d_batch: preds {tuple(preds.shape)} must match gts {tuple(gts.shape)}")
+    B, _, H, W = gts.shape
+    if B == 0 or H * W == 0:
+        raise ValueError("eval_3d_batch: empty batch or empty maps")
+    if not isinstance(masks, torch.Tensor) or tuple(masks.shape) not in ((B, 1, H, W), (B, H, W)):
+        raise ValueError(f"eval_3d_batch: masks must be [B,1,H,W] or [B,H,W] matching gts, got {tuple(getattr(masks, 'shape', ()))}")
+    if isinstance(thresholds, torch.Tensor):
+        if thresholds.ndim != 1 or thresholds.is_complex():
+            raise ValueError(f"eval_3d_batch: thresholds must be a 1-D real tensor, got {tuple(thresholds.shape)} {thresholds.dtype}")
+        T = thresholds.shape[0]
+    else:
+        try:
+            thresholds = [float(v) for v in thresholds]
+        except TypeError as e:
+            raise ValueError("eval_3d_batch: thresholds must be a list of floats or a 1-D tensor") from e
+        T = len(thresholds)
+    if not 1 <= T <= _lib.UD_EVAL3D_MAX_T:
+        raise ValueError(f"eval_3d_batch: 1 <= len(thresholds) <= {_lib.UD_EVAL3D_MAX_T} expected, got {T}")
+    if B > _lib.UD_EVAL3D_MAX_B:
+        raise ValueError(f"eval_3d_batch: at most {_lib.UD_EVAL3D_MAX_B} images per call, got {B}")
+    nbytes = int(_lib.lib.ud_eval_3d_work_bytes(B, H, W, T))
+    if nbytes < 0:
+        raise ValueError(f"eval_3d_batch: unsupported sizes B={B} H={H} W={W} T={T}")
+    if not (gts.is_cuda and preds.is_cuda and masks.is_cuda):
+        raise RuntimeError("eval_3d_batch: GPU tensors expected (the HIP kernels are the only implementation)")
+    dev = gts.device
+    th = torch.as_tensor(thresholds, device=dev).to(torch.float32).contiguous()
+    gt = gts.float().contiguous()
+    pred = preds.float().contiguous()
+    mask = masks.reshape(B, H, W).to(torch.bool).contiguous().view(torch.uint8)
+    out = torch.empty(len(EVAL_3D_KEYS), B, device=dev, dtype=torch.float32)
+    counts = torch.empty(B, device=dev, dtype=torch.int64)
+    size = torch.empty(2, device=dev, dtype=torch.int32)
+    work = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    d = mk(_lib.UdEval3d, gt=gt, pred=pred, mask=mask, thresholds=th, out=out, counts=counts, size=size, work=work, work_bytes=nbytes,
+           B=B, H=H, W=W, T=T)
+    check(_lib.lib.ud_eval_3d(d, cur_stream()), "ud_eval_3d")
+    res = {name: out[k] for k, name in enumerate(EVAL_3D_KEYS)}
+    res["count"] = counts
+    res["size"] = size
+    return res
+
+
+class MetricsAccumulator:
+    """The reference's metrics_store / metrics_count / get_evaluation (datasets/base_dataset.py:219-271) for ONE process: the rows of
+    every batch are kept on the device and reduced once at the end of the dataset.
+
+        acc = MetricsAccumulator(min_depth, max_depth)
+        for batch in loader:
+            acc.accumulate_depth(gts, preds, masks)            # eval_depth's 18 rows, masked at max_depth
+            acc.accumulate_3d(gt_points, pred_points, masks)   # eval_3d_batch's 3 rows with thresholds_3d(min_depth, max_depth)
+        metrics = acc.get_evaluation()                         # {key: round(mean, 5)}; the only place that synchronises
+
+    3-D keys average over the rows with count > 0, because the reference never stored the others; depth keys average plainly, as the
+    reference does, so a NaN row (an image without a valid pixel) propagates.  The cross-rank gather of the reference
+    (sync_tensor_across_gpus before the mean) is out of scope: every process reduces what it accumulated."""
+
+    def __init__(self, min_depth: float = 0.01, max_depth: float = 1000.0):
+        self.min_depth, self.max_depth = float(min_depth), float(max_depth)
+        self._rows = {}                                  # key -> list of [B] tensors
+        self._keep = {}                                  # key -> list of [B] bool tensors (3-D keys only)
+        self._thresholds = {}
+
+    def accumulate_depth(self, gts: torch.Tensor, preds: torch.Tensor, masks: torch.Tensor, name: str = "") -> None:
+        for key, row in eval_depth(gts, preds, masks, max_depth=self.max_depth).items():
+            self._rows.setdefault(f"{name}_{key}".strip("_"), []).append(row)
+
+    def accumulate_3d(self, gts: torch.Tensor, preds: torch.Tensor, masks: torch.Tensor, name: str = "") -> None:
+        dev = (gts.device.type, gts.device.index)
+        if dev not in self._thresholds:
+            self._thresholds[dev] = thresholds_3d(self.min_depth, self.max_depth, device=gts.device)
+        res = eval_3d_batch(gts, preds, masks, self._thresholds[dev])
+        keep = res["count"] > 0
+        for key in EVAL_3D_KEYS:
+            full = f"{name}_{key}".strip("_")
+            self._rows.setdefault(full, []).append(res[key])
+            self._keep.setdefault(full, []).append(keep)
+
+    def get_evaluation(self) -> dict:
+        """{key: round(mean over the accumulated rows, 5)}; clears the store."""
+        out = {}
+        for key, rows in self._rows.items():
+            v = torch.cat(rows)
+            if key in self._keep:
+                v = v[torch.cat(self._keep[key])]
+            out[key] = float(np.round(v.mean().item(), 5))
+        self._rows, self._keep = {}, {}
+        return out
