@@ -544,6 +544,33 @@ typedef struct UdEval3d {
 } UdEval3d;
 int ud_eval_3d(const UdEval3d* desc, void* stream);
 long long ud_eval_3d_work_bytes(int B, int H, int W, int T);
+/* Ground-truth point maps of a batch: the device form of Camera.reconstruct (utils/camera.py; datasets/base_dataset.py add_points),
+ * one camera model per image, stream-ordered, no host synchronisation (csrc/reconstruct.hip).
+ *   depth fp32 [B,1,H,W]; params fp32 [B,16] on the device, rows zero-padded, layouts as in csrc/camera_models.h (Pinhole fx fy cx cy;
+ *   EUCM + alpha beta; Spherical + W H hfov/2 vfov/2); model[b] = 1 Pinhole, 2 EUCM, 3 Spherical, 4 OPENCV, 5 Fisheye624, 6 MEI.
+ *   points fp32 [B,3,H,W].  Pixel centres are u + 0.5, v + 0.5; every maximum lets a NaN through (`x < m ? m : x`):
+ *     Pinhole     r = K^-1 [u, v, 1] = ((u - cx) / fx, (v - cy) / fy, 1), no skew;  r / max(r.z, 1e-4) * max(depth, 0)
+ *     Spherical   the unit-sphere direction, re-normalised with the 1e-5 floor, * depth (no clamp: a negative depth passes through)
+ *     EUCM        r = (c mx, c my, max(c mz, 1e-3));                              r / max(r.z, 1e-4) * max(depth, 1e-4)
+ *     OPENCV, Fisheye624   r = (dx, dy, 1) of the solvers, not normalised;        same formula
+ *     MEI         r = (dx, dy, pz), not normalised (pz <= 0 at wide angles: the 1e-4 floor decides);  same formula
+ *   A batch without an OPENCV / Fisheye624 member is one launch.  With n_iterative > 0 such members: one init launch (it also does every
+ *   closed-form image), 10 trust-region step launches over the iterative images only, one final launch, whatever B is.  Every iterative
+ *   image leaves the radial loop on its own, once ITS largest |residual| is below 1e-3 (the reference runs each member of a BatchCamera
+ *   separately); the maxima are cleared by the call (a memset node on `stream`), so a captured graph can be replayed.
+ *   work: device scratch, 16-byte aligned, of at least ud_reconstruct_work_bytes(B, H, W, n_iterative) bytes (host-only query; -1 for
+ *   sizes outside the limits; 0 and work may be NULL when n_iterative = 0): 11 maxima and a float4 solver state per pixel of every
+ *   iterative image.  Limits: 1 <= B <= UD_RECON_MAX_B, H, W >= 1, H * W < 2^31 - 256.  Built with -ffp-contract=off: every operation
+ *   rounds separately. */
+#define UD_RECON_MAX_B 256
+typedef struct UdReconstruct {
+  const float* depth; const float* params; float* points;
+  void* work; long long work_bytes;
+  int B, H, W;
+  unsigned char model[UD_RECON_MAX_B];
+} UdReconstruct;
+int ud_reconstruct(const UdReconstruct* desc, void* stream);
+long long ud_reconstruct_work_bytes(int B, int H, int W, int n_iterative);
 
 /* ---- output side: the valid pixels of a batch of predictions as packed point-cloud rows (csrc/pointcloud.hip) ----
  * The device form of the reference's get_pointcloud_from_rgbd (unidepth/utils/visualization.py:57-104: numpy, one image per call) for a
@@ -824,7 +851,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25; 16, 19, 22 and 24 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27; 16, 19, 22, 24 and 26 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

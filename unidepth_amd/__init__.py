@@ -12,7 +12,8 @@ _MATCHING = ("match_gt", "match_intrinsics")
 _VISUALIZATION = ("colorize", "colorize_batch", "demo_panel", "image_grid", "save_png", "preload_colormap")
 _REPROJECT = ("RenderedView", "render_depth", "reproject", "project_points", "downsample")
 _TESTPREP = ("TestGeometry", "test_geometry", "prepare_test_batch", "resize_aa", "original_image")
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP]
+_GTPOINTS = ("gt_points", "add_points", "prepare_camera")
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS]
 
 
 def __getattr__(name):
@@ -37,4 +38,7 @@ def __getattr__(name):
     if name in _TESTPREP:                             # validation inputs from raw uint8 images (testprep.py, csrc/testprep.hip)
         from . import testprep
         return getattr(testprep, name)
+    if name in _GTPOINTS:                             # ground-truth point maps for the validation loop (gtpoints.py, csrc/reconstruct.hip)
+        from . import gtpoints
+        return getattr(gtpoints, name)
     raise AttributeError(name)

@@ -103,6 +103,14 @@ class UdEval3d(C.Structure):
                 ("work", vp), ("work_bytes", i64), ("B", i32), ("H", i32), ("W", i32), ("T", i32)]
 
 
+UD_RECON_MAX_B = 256
+
+
+class UdReconstruct(C.Structure):
+    _fields_ = [("depth", vp), ("params", vp), ("points", vp), ("work", vp), ("work_bytes", i64), ("B", i32), ("H", i32), ("W", i32),
+                ("model", C.c_ubyte * UD_RECON_MAX_B)]
+
+
 UD_PC_MINCONF, UD_PC_RANGE, UD_PC_EDGE, UD_PC_FLIP_Y = 1, 2, 4, 8
 
 
@@ -277,6 +285,7 @@ def _load():
         "ud_extract_patches": [P(UdExtractPatches), vp],
         "ud_eval_depth": [P(UdEvalDepth), vp],
         "ud_eval_3d": [P(UdEval3d), vp],
+        "ud_reconstruct": [P(UdReconstruct), vp],
         "ud_pointcloud_pack": [P(UdPointCloud), vp],
         "ud_match_gt": [P(UdMatchGt), vp],
         "ud_colorize": [P(UdColorize), vp],
@@ -301,14 +310,16 @@ def _load():
     lib.ud_eval_depth_work_bytes.restype = i64
     lib.ud_eval_3d_work_bytes.argtypes = [i32, i32, i32, i32]
     lib.ud_eval_3d_work_bytes.restype = i64
+    lib.ud_reconstruct_work_bytes.argtypes = [i32, i32, i32, i32]
+    lib.ud_reconstruct_work_bytes.restype = i64
     lib.ud_pointcloud_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_pointcloud_work_bytes.restype = i64
     lib.ud_colorize_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d]):
-        if st is None:                                  # indices 16, 19, 22 and 24 are not assigned: the library answers -1
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct]):
+        if st is None:                                  # indices 16, 19, 22, 24 and 26 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

@@ -13,6 +13,7 @@ Only what the infer() path needs is here: the bookkeeping that maps a camera of 
 :336-357) and a tag for the ray kernel (ud_rays_from_kinv gt_mode).  The unprojection itself runs on the GPU
 (csrc/pointwise.hip rays_kernel; the iterative models -- OPENCV, Fisheye624, MEI -- through ud_rays_from_camera, which
 reproduces the reference's Newton / trust-region solvers including the image-wide early exit of the radial loop).  Unlike the reference, infer() does not modify the camera object it is given.
+Camera.reconstruct(depth), on every class, is the ground-truth point map of the validation loop (gtpoints.py, csrc/reconstruct.hip).
 Objects of the reference's own classes are accepted as well (matched by class name and `.params`)."""
 from __future__ import annotations
 
@@ -46,6 +47,12 @@ class Camera:
         p[:, 3] += pt
         p[:, :4] *= resize_factor
         return p
+
+    def reconstruct(self, depth: torch.Tensor) -> torch.Tensor:
+        """The reference's Camera.reconstruct: depth [B,1,H,W] or [B,H,W] on the GPU -> ground-truth points fp32 [B,3,H,W]
+        (gtpoints.gt_points, csrc/reconstruct.hip).  The camera is not modified."""
+        from .gtpoints import gt_points
+        return gt_points(depth, self)
 
 
 class Pinhole(Camera):

@@ -36,6 +36,9 @@ done
 # eval_3d: |gt - pred| and the nearest-neighbour distances (knn_dist.h, shared with evalops.hip) round every multiply and add
 # separately, so the distances are bit-equal to ud_knn_points' and a numpy fp32 restatement reproduces the threshold counts, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c eval3d.hip -o $BD/eval3d.o ) & pids+=($!)
+# reconstruct: the ground-truth point maps are defined operation by operation in fp32 (camera_models.h under this flag is what the numpy
+# fp32 restatement and the host build of the tests compute), same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c reconstruct.hip -o $BD/reconstruct.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)

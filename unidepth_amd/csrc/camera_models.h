@@ -134,3 +134,45 @@ UD_CAM_FN void ud_cam_mei(const float* p, float u, float v, float& x, float& y, 
   const float inv = 1.0f / fmaxf(sqrtf(dx * dx + dy * dy + pz * pz), 1e-4f);
   x = dx * inv; y = dy * inv; z = pz * inv;
 }
+
+// ---- the same directions NOT normalised: what Camera.reconstruct (camera.py:69-76) divides by its z and multiplies with the depth
+// (reconstruct.hip).  Separate functions, the same operations in the same order: the normalised ones above stay exactly as they
+// were, so the ray kernels that inline them compile to the same code.  The solver bodies are therefore duplicated and must be kept in
+// step by hand: test_unnormalised_header_functions_on_the_host (tests/test_gt_points_cpu.py, through tests/recon_host) fails when
+// normalising one of these no longer reproduces its twin above bit for bit.
+// ud_cam_finish_radial without the normalisation: (dx, dy), z = 1, as unproject() returns it (camera.py:687-694, :967-974).
+UD_CAM_FN void ud_cam_finish_radial_dir(float xr, float yr, float rnorm, float th, int tan_theta, float& dx, float& dy) {
+  const bool close = fabsf(th) < UD_CAM_EPS && fabsf(rnorm) < UD_CAM_EPS;
+  const float sc = (tan_theta ? tanf(th) : th) / rnorm;
+  dx = close ? xr : sc * xr;
+  dy = close ? yr : sc * yr;
+}
+
+// ud_cam_mei without the normalisation: (dx, dy, pz) as MEI.unproject returns it (camera.py:1063-1081); pz is <= 0 beyond the
+// mirror's horizon.
+UD_CAM_FN void ud_cam_mei_dir(const float* p, float u, float v, float& dx, float& dy, float& pz) {
+  const float k1 = p[4], k2 = p[5], p0 = p[6], p1 = p[7], xi = p[8];
+  const int use_radial = fabsf(k1) + fabsf(k2) > 1e-6f;
+  const int use_tan = fabsf(p0) + fabsf(p1) > 1e-6f;
+  const float ud = (u - p[2]) / p[0], vd = (v - p[3]) / p[1];
+  float xr, yr;
+  ud_cam_undistort_tanprism(ud, vd, p0, p1, 0.f, 0.f, 0.f, 0.f, 1, 0, use_tan ? 20 : 0, xr, yr);
+  const float rnorm = sqrtf(xr * xr + yr * yr);
+  float th = rnorm;
+  for (int it = 0; it < (use_radial ? 20 : 0); ++it) {
+    const float t2 = th * th, t4 = t2 * t2;
+    const float thr = (1.0f + k1 * t2 + k2 * t4) * th;
+    const float dth = 1.0f + 3.0f * k1 * t2 + 5.0f * k2 * t4;
+    float step = (rnorm - thr) / dth;
+    if (!(fabsf(dth) > UD_CAM_EPS_MEI)) step = (step > 0.f ? 1.f : (step < 0.f ? -1.f : 0.f)) * UD_CAM_EPS_MEI * 10.0f;
+    th = th + step;
+  }
+  const bool close = fabsf(th) < UD_CAM_EPS_MEI && fabsf(rnorm) < UD_CAM_EPS_MEI;
+  dx = close ? xr : th * xr / rnorm;
+  dy = close ? yr : th * yr / rnorm;
+  const float rho = sqrtf(dx * dx + dy * dy);
+  const float rho2 = rho * rho;
+  const float sq = sqrtf(1.0f + (1.0f - xi * xi) * rho2);
+  pz = 1.0f - xi * (rho2 + 1.0f) / (xi + sq);
+  if (xi == 1.0f) pz = (1.0f - rho2) / 2.0f;
+}

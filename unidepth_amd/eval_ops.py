@@ -388,6 +388,7 @@ class MetricsAccumulator:
         for batch in loader:
             acc.accumulate_depth(gts, preds, masks)            # eval_depth's 18 rows, masked at max_depth
             acc.accumulate_3d(gt_points, pred_points, masks)   # eval_3d_batch's 3 rows with thresholds_3d(min_depth, max_depth)
+            # or both, with the ground-truth points made from the depth and the camera:  acc.accumulate_metrics(inputs, preds)
         metrics = acc.get_evaluation()                         # {key: round(mean, 5)}; the only place that synchronises
 
     3-D keys average over the rows with count > 0, because the reference never stored the others; depth keys average plainly, as the
@@ -414,6 +415,29 @@ class MetricsAccumulator:
             full = f"{name}_{key}".strip("_")
             self._rows.setdefault(full, []).append(res[key])
             self._keep.setdefault(full, []).append(keep)
+
+    def accumulate_metrics(self, inputs: dict, preds: dict, keyframe_idx: Optional[int] = None) -> None:
+        """The reference's accumulate_metrics (datasets/base_dataset.py:186-216) for depth and points: inputs holds "depth",
+        "depth_mask", "camera" (and "camera_original" when the ground truth is at the raw image's size; optionally "points",
+        "points_mask"), preds the prediction tensors by key.  Ground-truth points are added first when inputs has a depth and no points
+        (gtpoints.add_points); with keyframe_idx only that image of the batch is evaluated; every prediction key that contains "depth"
+        goes through accumulate_depth, every key that contains "points" through accumulate_3d (points_mask if present, else
+        depth_mask), each under the name the reference derives from the key.  A metric missing from either side is skipped."""
+        if "depth" in inputs and "points" not in inputs:
+            from .gtpoints import add_points
+            inputs = add_points(inputs)
+        available = [m for m in ("depth", "points") if any(m in k for k in inputs) and any(m in k for k in preds)]
+        sl = slice(None) if keyframe_idx is None else slice(keyframe_idx, keyframe_idx + 1)
+        if "depth" in available:
+            gts, masks = inputs["depth"][sl], inputs["depth_mask"][sl].bool()
+            for key, pred in preds.items():
+                if "depth" in key:
+                    self.accumulate_depth(gts, pred[sl], masks, name=key.replace("depth", "").strip("-").strip("_"))
+        if "points" in available:
+            gts, masks = inputs["points"][sl], inputs.get("points_mask", inputs["depth_mask"])[sl].bool()
+            for key, pred in preds.items():
+                if "points" in key:
+                    self.accumulate_3d(gts, pred[sl], masks, name=key.replace("points", "").strip("-").strip("_"))
 
     def get_evaluation(self) -> dict:
         """{key: round(mean over the accumulated rows, 5)}; clears the store."""
