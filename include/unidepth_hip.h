@@ -572,6 +572,37 @@ typedef struct UdReconstruct {
 int ud_reconstruct(const UdReconstruct* desc, void* stream);
 long long ud_reconstruct_work_bytes(int B, int H, int W, int n_iterative);
 
+/* The other direction: the points of a batch projected to image coordinates, the device form of Camera.project (utils/camera.py:
+ * Pinhole :239-252, EUCM :281-304, Spherical :359-368, OPENCV :423-493, Fisheye624 :705-775, MEI :1084-1142, BatchCamera :1158-1164),
+ * one camera model per image, in ONE launch with one thread per point (csrc/project.hip; the arithmetic is csrc/camera_models.h
+ * ud_cam_project_<model>).  Stream-ordered, no host synchronisation, no work buffer.
+ *   xyz fp32: coordinate c of point r of image b is at xyz[b * batch_stride + r * point_stride + c * comp_stride] (ELEMENTS), as UdSplat:
+ *     planar [B,3,h,w] is (3hw, 1, hw), rows [B,N,3] are (3N, 3, 1); comp_stride = 1 rows are read with one 12-byte load.
+ *   params fp32 [B,16] and model[b] as UdReconstruct.  T fp32 [nT,3,4] (nT = 1 or B; NULL = none): a rigid motion applied first, with
+ *     UdSplat's arithmetic (x' = ((t00*x + t01*y) + t02*z) + t03, ...).
+ *   Per model, every operation rounded separately, every maximum letting a NaN through:
+ *     Pinhole     u = (fx*x + cx*z) / max(z, 0.01), v likewise (the skew-free K of the row)
+ *     EUCM        d = sqrt(beta*(x*x + y*y) + z*z), den = max(alpha*d + (1 - alpha)*z, 1e-3), u = fx*(x/den) + cx
+ *     Spherical   lon = atan2(x, z), lat = asin(y / max(|xyz|, 1e-5)), u = lon / (2 hfov2) * (Wp - 1) + (Wp - 1) / 2 with the ROW's Wp, Hp
+ *     OPENCV      z -> 1e-9 sign(z) when |z| < 1e-9 (sign(0) = 0); ab = xy / z, r = |ab|; ab * (1 + k1 r^2 + k2 r^4 + k3 r^6); tangential
+ *                 u += (2 xr^2 + rd) p0 + 2 xr yr p1 (v mirrored), thin prism u += s0 rd + s1 rd^2, v += s2 rd + s3 rd^2; then * f + c
+ *     Fisheye624  the same front end; th = atan(r), th_k = th + sum_j k_j th^(3+2j) (j < 6) along ab / r (1, 1 where r < 1e-9); same tail
+ *     MEI         ab = xy / (z + xi |xyz|); ab * (1 + k1 r^2 + k2 r^4); tangential (p at positions 6, 7); * f + c
+ *   outputs: uv fp32, planar [B,2,n_points] (uv_rows = 0) or rows [B,n_points,2] (uv_rows != 0; one 8-byte store);
+ *     inside uint8 [B,n_points] (optional): the model's own in-image test against the descriptor's H, W, comparisons as in the reference
+ *       (Pinhole u >= 0 & u < W & v >= 0 & v < H; EUCM !(u < 0 | u > W | v < 0 | v > H | z' < 0); the others the same without z');
+ *     depth fp32 [B,n_points] (optional): the model's depth of the point, z', or |xyz'| for Spherical -- what UdReconstruct multiplies with.
+ *   Limits: 1 <= B <= UD_RECON_MAX_B, H, W >= 1, 0 <= n_points < 2^31, point_stride, comp_stride >= 1, batch_stride >= 0.  Every refusal
+ *   is returned before any HIP call. */
+typedef struct UdCameraProject {
+  const float* xyz; const float* params; const float* T;
+  float* uv; unsigned char* inside; float* depth;
+  long long batch_stride, point_stride, comp_stride, n_points;
+  int B, H, W, nT, uv_rows;
+  unsigned char model[UD_RECON_MAX_B];
+} UdCameraProject;
+int ud_camera_project(const UdCameraProject* desc, void* stream);
+
 /* ---- output side: the valid pixels of a batch of predictions as packed point-cloud rows (csrc/pointcloud.hip) ----
  * The device form of the reference's get_pointcloud_from_rgbd (unidepth/utils/visualization.py:57-104: numpy, one image per call) for a
  * whole batch: an ordered, deterministic stream compaction in a few plain launches on `stream` (flag + count, scan, pack), no atomics,
@@ -742,6 +773,26 @@ typedef struct UdSplat {
 int ud_splat(const UdSplat* desc, void* stream);
 long long ud_splat_work_bytes(int B, int H, int W);
 
+/* ud_splat with the projection K (x', y', z') replaced by the camera model of the point's image (UdCameraProject's models and parameter
+ * rows): the same three launches, work layout (ud_splat_work_bytes), modes, TRUNC / RANGE flags, outputs and packed offsets.
+ *   (u, v) = the model's projection of (x', y', z'); the cell comes from u + pixel_offset, v + pixel_offset as in UdSplat.
+ *   The depth of a point -- keyed in nearest mode, summed in mean mode, tested by UD_SPLAT_RANGE -- is the model's depth: z', or
+ *   |xyz'| for Spherical.  Nearest mode drops !(depth > 0).  In both modes every model but Spherical drops z' <= 0, MEI additionally keeps a
+ *   point only if z' + xi |xyz'| > 0, and with UD_SPLAT_FOV a point is kept only if z' >= cos_limit * |xyz'| (the polynomial models fold
+ *   points far off the axis back into the image: this is how a caller culls them).
+ *   Limits as UdSplat, with 1 <= B <= UD_RECON_MAX_B.  Every refusal is returned before any HIP call. */
+enum { UD_SPLAT_FOV = 4 };                            /* UdSplatCamera.flags only, beside UD_SPLAT_TRUNC and UD_SPLAT_RANGE */
+typedef struct UdSplatCamera {
+  const float* xyz; const long long* offsets; const float* params; const float* T; const void* color;
+  float* depth; int* index; void* rgb; int* count;
+  void* work; long long work_bytes;
+  long long batch_stride, point_stride, comp_stride, n_points;
+  int B, H, W, nT, mode, flags, color_f32;
+  float pixel_offset, dmin, dmax, cos_limit;
+  unsigned char model[UD_RECON_MAX_B];
+} UdSplatCamera;
+int ud_splat_camera(const UdSplatCamera* desc, void* stream);
+
 /* The reference's `downsample` (unidepth/utils/geometric.py:208-224), a hole-aware min-pool of sparse depth maps, in one launch:
  * src fp32 [N,1,H,W] contiguous -> dst fp32 [N,1,H/factor,W/factor].  Every value == 0 (either sign) of a factor x factor block counts as
  * 1e5f; the output is the block's minimum, written as 0 when it is > 1000, and NaN when the block holds a NaN (torch.min).  Exact.
@@ -851,7 +902,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27; 16, 19, 22, 24 and 26 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29; 16, 19, 22, 24 and 26 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

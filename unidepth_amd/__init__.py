@@ -10,7 +10,7 @@ from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
 _POINTCLOUD = ("PointCloud", "pack_points", "from_prediction", "get_pointcloud_from_rgbd", "save_ply", "save_file_ply")
 _MATCHING = ("match_gt", "match_intrinsics")
 _VISUALIZATION = ("colorize", "colorize_batch", "demo_panel", "image_grid", "save_png", "preload_colormap")
-_REPROJECT = ("RenderedView", "render_depth", "reproject", "project_points", "downsample")
+_REPROJECT = ("RenderedView", "render_depth", "reproject", "project_points", "downsample", "render_depth_camera", "project_camera")
 _TESTPREP = ("TestGeometry", "test_geometry", "prepare_test_batch", "resize_aa", "original_image")
 _GTPOINTS = ("gt_points", "add_points", "prepare_camera")
 __all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS]
@@ -32,7 +32,7 @@ def __getattr__(name):
     if name in _VISUALIZATION:                        # depth maps as colour images (visualization.py, csrc/colorize.hip)
         from . import visualization
         return getattr(visualization, name)
-    if name in _REPROJECT:                            # point clouds back into depth maps (reproject.py, csrc/splat.hip)
+    if name in _REPROJECT:                            # point clouds back into depth maps (reproject.py, csrc/splat.hip, csrc/project.hip)
         import importlib                              # not `from . import reproject`: that asks this function for "reproject" first
         return getattr(importlib.import_module(".reproject", __name__), name)
     if name in _TESTPREP:                             # validation inputs from raw uint8 images (testprep.py, csrc/testprep.hip)

@@ -111,6 +111,12 @@ class UdReconstruct(C.Structure):
                 ("model", C.c_ubyte * UD_RECON_MAX_B)]
 
 
+class UdCameraProject(C.Structure):
+    _fields_ = [("xyz", vp), ("params", vp), ("T", vp), ("uv", vp), ("inside", vp), ("depth", vp),
+                ("batch_stride", i64), ("point_stride", i64), ("comp_stride", i64), ("n_points", i64),
+                ("B", i32), ("H", i32), ("W", i32), ("nT", i32), ("uv_rows", i32), ("model", C.c_ubyte * UD_RECON_MAX_B)]
+
+
 UD_PC_MINCONF, UD_PC_RANGE, UD_PC_EDGE, UD_PC_FLIP_Y = 1, 2, 4, 8
 
 
@@ -158,6 +164,16 @@ class UdSplat(C.Structure):
                 ("work", vp), ("work_bytes", i64), ("batch_stride", i64), ("point_stride", i64), ("comp_stride", i64), ("n_points", i64),
                 ("B", i32), ("H", i32), ("W", i32), ("nK", i32), ("nT", i32), ("mode", i32), ("flags", i32), ("color_f32", i32),
                 ("pixel_offset", f32), ("dmin", f32), ("dmax", f32)]
+
+
+UD_SPLAT_FOV = 4                                      # UdSplatCamera.flags only
+
+
+class UdSplatCamera(C.Structure):
+    _fields_ = [("xyz", vp), ("offsets", vp), ("params", vp), ("T", vp), ("color", vp), ("depth", vp), ("index", vp), ("rgb", vp), ("count", vp),
+                ("work", vp), ("work_bytes", i64), ("batch_stride", i64), ("point_stride", i64), ("comp_stride", i64), ("n_points", i64),
+                ("B", i32), ("H", i32), ("W", i32), ("nT", i32), ("mode", i32), ("flags", i32), ("color_f32", i32),
+                ("pixel_offset", f32), ("dmin", f32), ("dmax", f32), ("cos_limit", f32), ("model", C.c_ubyte * UD_RECON_MAX_B)]
 
 
 class UdDepthMinPool(C.Structure):
@@ -290,6 +306,8 @@ def _load():
         "ud_match_gt": [P(UdMatchGt), vp],
         "ud_colorize": [P(UdColorize), vp],
         "ud_splat": [P(UdSplat), vp],
+        "ud_splat_camera": [P(UdSplatCamera), vp],
+        "ud_camera_project": [P(UdCameraProject), vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
         "ud_program_run": [vp, i32, i32, vp],
@@ -318,7 +336,7 @@ def _load():
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct]):
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera]):
         if st is None:                                  # indices 16, 19, 22, 24 and 26 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:

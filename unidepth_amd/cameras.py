@@ -14,6 +14,7 @@ Only what the infer() path needs is here: the bookkeeping that maps a camera of 
 (csrc/pointwise.hip rays_kernel; the iterative models -- OPENCV, Fisheye624, MEI -- through ud_rays_from_camera, which
 reproduces the reference's Newton / trust-region solvers including the image-wide early exit of the radial loop).  Unlike the reference, infer() does not modify the camera object it is given.
 Camera.reconstruct(depth), on every class, is the ground-truth point map of the validation loop (gtpoints.py, csrc/reconstruct.hip).
+Camera.project(points) / get_projection_mask(), on every class, go the other way (reproject.project_camera, csrc/project.hip).
 Objects of the reference's own classes are accepted as well (matched by class name and `.params`)."""
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ GT_PINHOLE, GT_EUCM, GT_SPHERICAL, GT_OPENCV, GT_FISHEYE624, GT_MEI = 1, 2, 3, 4
 class Camera:
     gt_mode = 0
     n_params = 4
+    projection_mask = None                            # the mask of the last project() call (get_projection_mask)
 
     def __init__(self, params: torch.Tensor):
         params = torch.as_tensor(params, dtype=torch.float32)
@@ -54,6 +56,35 @@ class Camera:
         from .gtpoints import gt_points
         return gt_points(depth, self)
 
+    def project(self, points: torch.Tensor) -> torch.Tensor:
+        """The reference's Camera.project: points fp32 [B,3,H,W] on the GPU -> image coordinates fp32 [B,2,H,W], every image through its
+        own camera in one launch (reproject.project_camera, csrc/project.hip).  The image the mask is taken against is the point map's
+        own (H, W), as in the reference.  Remembers the mask of this call for get_projection_mask(); nothing else of the camera changes."""
+        from .reproject import project_camera
+        if not isinstance(points, torch.Tensor) or points.ndim != 4 or points.shape[1] != 3:
+            raise ValueError(f"{type(self).__name__}.project: points must be [B,3,H,W], got {tuple(getattr(points, 'shape', ()))}")
+        if not points.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.project: GPU tensors expected (the HIP kernels are the only implementation)")
+        uv, inside, _ = project_camera(points, self)
+        self.projection_mask = self._projection_mask(inside.unsqueeze(1))
+        return uv
+
+    def _projection_mask(self, inside: torch.Tensor):
+        return inside
+
+    def get_projection_mask(self):
+        """The mask of the last project() call, bool [B,1,H,W], with the reference's returns class by class:
+
+            EUCM, OPENCV, Fisheye624, MEI   True where the point projects into the image (EUCM: and z >= 0)
+            Pinhole                         INVERTED, deliberately: the reference names its inside test `invalid` and stores `~invalid`
+                                            (utils/camera.py:245-251), so True marks the points that fall OUTSIDE the image
+            Spherical                       None: the reference's project sets no mask
+            BatchCamera                     every image with its member's rule; a Spherical member gets the plain inside test (the
+                                            reference would fail there, on torch.cat of None)
+
+        None before the first project()."""
+        return self.projection_mask
+
 
 class Pinhole(Camera):
     gt_mode = GT_PINHOLE
@@ -64,6 +95,9 @@ class Pinhole(Camera):
             params = torch.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], dim=1)
         super().__init__(params)
 
+    def _projection_mask(self, inside):
+        return ~inside                                # the reference's inversion, see get_projection_mask
+
 
 class EUCM(Camera):
     gt_mode = GT_EUCM
@@ -73,6 +107,9 @@ class EUCM(Camera):
 class Spherical(Camera):
     gt_mode = GT_SPHERICAL
     n_params = 8
+
+    def _projection_mask(self, inside):
+        return None
 
     def network_params(self, paddings, resize_factor: float) -> torch.Tensor:
         pl, pr, pt, pb = paddings
@@ -134,6 +171,10 @@ class BatchCamera(Camera):
     @property
     def gt_modes(self):
         return tuple(c.gt_mode for c in self.cameras)
+
+    def _projection_mask(self, inside):
+        flip = torch.tensor([isinstance(c, Pinhole) for c in self.cameras]).to(inside.device)
+        return inside ^ flip[:, None, None, None]
 
     def uniform(self):
         cls = type(self.cameras[0])

@@ -39,6 +39,9 @@ done
 # reconstruct: the ground-truth point maps are defined operation by operation in fp32 (camera_models.h under this flag is what the numpy
 # fp32 restatement and the host build of the tests compute), same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c reconstruct.hip -o $BD/reconstruct.o ) & pids+=($!)
+# project: the image coordinates of a point are defined operation by operation in fp32 (the forward models of camera_models.h under this
+# flag are what the numpy fp32 restatement and the host build of the tests compute), same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c project.hip -o $BD/project.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)

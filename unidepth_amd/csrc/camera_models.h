@@ -176,3 +176,121 @@ UD_CAM_FN void ud_cam_mei_dir(const float* p, float u, float v, float& dx, float
   pz = 1.0f - xi * (rho2 + 1.0f) / (xi + sq);
   if (xi == 1.0f) pz = (1.0f - rho2) / 2.0f;
 }
+
+// ---- the forward models: Camera.project of every class (camera.py: Pinhole :239-252, EUCM :281-304, Spherical :359-368, OPENCV :423-493,
+// Fisheye624 :705-775, MEI :1084-1142), a camera-frame point (x, y, z) -> image coordinates (u, v).  Closed form, operation by operation
+// in the reference's order, so that the numpy fp32 restatement of tools/make_golden_camera_project.py reproduces them (project.hip and
+// splat.hip are built with -ffp-contract=off; tests/proj_host compiles this header for the host).  `p` is the 16-float parameter row of
+// UdReconstruct.  Model tags as UdReconstruct.model.
+enum { UD_CAM_PINHOLE = 1, UD_CAM_EUCM = 2, UD_CAM_SPHERICAL = 3, UD_CAM_OPENCV = 4, UD_CAM_FISHEYE624 = 5, UD_CAM_MEI = 6 };
+
+// max(x, m) that lets a NaN through, as torch.clamp(min=m) does
+UD_CAM_FN float ud_cam_floor(float x, float m) { return x < m ? m : x; }
+
+// K (x, y, z) of the skew-free K built from the row, divided by max(w, 0.01) (camera.py:242-243)
+UD_CAM_FN void ud_cam_project_pinhole(const float* p, float x, float y, float z, float* u, float* v) {
+  const float zc = ud_cam_floor(z, 0.01f);
+  *u = (p[0] * x + p[2] * z) / zc;
+  *v = (p[1] * y + p[3] * z) / zc;
+}
+
+UD_CAM_FN void ud_cam_project_eucm(const float* p, float x, float y, float z, float* u, float* v) {
+  const float al = p[4], be = p[5];
+  const float d = sqrtf(be * (x * x + y * y) + z * z);
+  const float den = ud_cam_floor(al * d + (1.0f - al) * z, 1e-3f);
+  *u = p[0] * (x / den) + p[2];
+  *v = p[1] * (y / den) + p[3];
+}
+
+// equirectangular: W, H are the row's own values (p[4], p[5]), the half fields of view p[6], p[7]
+UD_CAM_FN void ud_cam_project_spherical(const float* p, float x, float y, float z, float* u, float* v) {
+  const float lon = atan2f(x, z);
+  const float lat = asinf(y / ud_cam_floor(sqrtf(x * x + y * y + z * z), 1e-5f));
+  *u = lon / (2.0f * p[6]) * (p[4] - 1.0f) + (p[4] - 1.0f) / 2.0f;
+  *v = lat / (2.0f * p[7]) * (p[5] - 1.0f) + (p[5] - 1.0f) / 2.0f;
+}
+
+// the shared front end of OPENCV and Fisheye624: z replaced by eps * sign(z) when |z| < eps = 1e-9 (sign(0) = 0, so z = 0 divides by
+// zero as in the reference), ab = xy / z, r = |ab|
+UD_CAM_FN void ud_cam_project_front(float x, float y, float z, float* a, float* b, float* r) {
+  const float sg = z > 0.0f ? 1.0f : (z < 0.0f ? -1.0f : 0.0f);
+  const float zz = fabsf(z) < 1e-9f ? 1e-9f * sg : z;
+  *a = x / zz;
+  *b = y / zz;
+  *r = sqrtf(*a * *a + *b * *b);
+}
+
+// the shared back end: tangential (p0, p1), thin prism (s = s0..s3, or null for MEI), focal lengths and principal point
+UD_CAM_FN void ud_cam_project_back(const float* p, float xr, float yr, float p0, float p1, const float* s, float* u, float* v) {
+  const float xr2 = xr * xr, yr2 = yr * yr;
+  const float rd = xr2 + yr2;
+  float ud = xr + ((2.0f * xr2 + rd) * p0 + 2.0f * xr * yr * p1);
+  float vd = yr + ((2.0f * yr2 + rd) * p1 + 2.0f * xr * yr * p0);
+  if (s) {
+    const float rd4 = rd * rd;
+    ud = ud + (s[0] * rd + s[1] * rd4);
+    vd = vd + (s[2] * rd + s[3] * rd4);
+  }
+  *u = ud * p[0] + p[2];
+  *v = vd * p[1] + p[3];
+}
+
+// radial numerator 1 + k1 r^2 + k2 r^4 + k3 r^6; the denominator is 1: k4..k6 are refused when the camera is constructed
+UD_CAM_FN void ud_cam_project_opencv(const float* p, float x, float y, float z, float* u, float* v) {
+  float a, b, r;
+  ud_cam_project_front(x, y, z, &a, &b, &r);
+  const float r2 = r * r, r4 = r2 * r2, r6 = r4 * r2;
+  const float num = 1.0f + ((r2 * p[4] + r4 * p[5]) + r6 * p[6]);
+  ud_cam_project_back(p, a * num, b * num, p[10], p[11], p + 12, u, v);
+}
+
+// th = atan(r), th_k = th + sum_j k_j th^(3+2j), along ab / r (1 for BOTH components where r < 1e-9: the reference's ones_like)
+UD_CAM_FN void ud_cam_project_fisheye624(const float* p, float x, float y, float z, float* u, float* v) {
+  float a, b, r;
+  ud_cam_project_front(x, y, z, &a, &b, &r);
+  const float th = atanf(r);
+  const float dx = r < 1e-9f ? 1.0f : a / r, dy = r < 1e-9f ? 1.0f : b / r;
+  const float t2 = th * th;
+  float pw = th * t2, s = 0.0f;
+  for (int j = 0; j < 6; ++j) {
+    s = s + pw * p[4 + j];
+    pw = pw * t2;
+  }
+  const float thk = th + s;
+  ud_cam_project_back(p, thk * dx, thk * dy, p[10], p[11], p + 12, u, v);
+}
+
+UD_CAM_FN void ud_cam_project_mei(const float* p, float x, float y, float z, float* u, float* v) {
+  const float n = sqrtf(x * x + y * y + z * z);
+  const float den = z + p[8] * n;
+  const float a = x / den, b = y / den;
+  const float r = sqrtf(a * a + b * b);
+  const float r2 = r * r, r4 = r2 * r2;
+  const float f = 1.0f + p[4] * r2 + p[5] * r4;
+  ud_cam_project_back(p, a * f, b * f, p[6], p[7], nullptr, u, v);
+}
+
+UD_CAM_FN void ud_cam_project(int model, const float* p, float x, float y, float z, float* u, float* v) {
+  switch (model) {
+    case UD_CAM_PINHOLE: ud_cam_project_pinhole(p, x, y, z, u, v); break;
+    case UD_CAM_EUCM: ud_cam_project_eucm(p, x, y, z, u, v); break;
+    case UD_CAM_SPHERICAL: ud_cam_project_spherical(p, x, y, z, u, v); break;
+    case UD_CAM_OPENCV: ud_cam_project_opencv(p, x, y, z, u, v); break;
+    case UD_CAM_FISHEYE624: ud_cam_project_fisheye624(p, x, y, z, u, v); break;
+    default: ud_cam_project_mei(p, x, y, z, u, v); break;
+  }
+}
+
+// the model's depth of a point, the quantity Camera.reconstruct multiplies its direction with: z, or the distance for Spherical
+UD_CAM_FN float ud_cam_depth(int model, float x, float y, float z) {
+  return model == UD_CAM_SPHERICAL ? sqrtf(x * x + y * y + z * z) : z;
+}
+
+// each class's own in-image test with the reference's comparisons taken literally (a NaN coordinate is "inside" for every model but
+// Pinhole, as it is there).  Spherical has no test in the reference: the OPENCV form.
+UD_CAM_FN bool ud_cam_inside(int model, float u, float v, float z, int H, int W) {
+  const float w = (float)W, h = (float)H;
+  if (model == UD_CAM_PINHOLE) return u >= 0.0f && u < w && v >= 0.0f && v < h;
+  if (model == UD_CAM_EUCM) return !(u < 0.0f || u > w || v < 0.0f || v > h || z < 0.0f);
+  return !(u < 0.0f || u > w || v < 0.0f || v > h);
+}

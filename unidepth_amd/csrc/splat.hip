@@ -13,8 +13,11 @@
 // Every dependency is a launch boundary: no tickets, no spinning, no host synchronisation, no float atomics.  Nearest mode is an
 // atomicMin on (bits(z') << 32 | r): z' > 0, so the integer order of the keys IS the (z', r) lexicographic order and the winner does not
 // depend on arrival order.  Mean mode sums llrintf(z' * 2^24) in an int64: integer addition is associative, so neither does the sum.
+// ud_splat_camera (UdSplatCamera) is the same three launches with the projector exchanged: sp_splat_kernel takes it as a template parameter,
+// SpProjMatrix (UdSplat's 3x3 matrix) or SpProjCamera (the camera model of the point's image, camera_models.h ud_cam_project).
 // Built with -ffp-contract=off: the cell a point lands in must be the one a numpy fp32 restatement computes.
 #include "ud_common.h"
+#include "camera_models.h"
 
 namespace {
 
@@ -64,8 +67,44 @@ __device__ __forceinline__ int sp_cell(float u, int n, bool trunc_mode) {
   return c < n ? c : -1;
 }
 
-template <bool ROWS>
-__global__ __launch_bounds__(SP_THREADS) void sp_splat_kernel(SpArgs a) {
+// The projector of a splat: (x', y', z') of a point of image b -> image coordinates (before pixel_offset) and the point's depth, or
+// false when the projector itself drops the point.
+// SpProjMatrix: UdSplat's full 3x3 matrix; the depth is z'.
+struct SpProjMatrix {
+  __device__ __forceinline__ bool operator()(const SpArgs& a, int b, float x, float y, float z, float& u, float& v, float& dep) const {
+    const float* k = a.K + (a.nK == 1 ? 0 : (size_t)b * 9);
+    const float pa = (k[0] * x + k[1] * y) + k[2] * z;
+    const float pb = (k[3] * x + k[4] * y) + k[5] * z;
+    const float pw = (k[6] * x + k[7] * y) + k[8] * z;
+    u = pa / pw;
+    v = pb / pw;
+    dep = z;
+    return true;
+  }
+};
+
+// SpProjCamera: UdSplatCamera's camera model of the image (camera_models.h); the depth is the model's (z', or the distance for Spherical)
+struct SpProjCamera {
+  const float* params;
+  float cos_limit;
+  unsigned char model[UD_RECON_MAX_B];
+  __device__ __forceinline__ bool operator()(const SpArgs& a, int b, float x, float y, float z, float& u, float& v, float& dep) const {
+    const int m = model[b];
+    const float* p = params + (size_t)b * 16;
+    if (m != UD_CAM_SPHERICAL && z <= 0.0f) return false;
+    if (m == UD_CAM_MEI || m == UD_CAM_SPHERICAL || (a.flags & UD_SPLAT_FOV)) {
+      const float n = sqrtf(x * x + y * y + z * z);
+      if (m == UD_CAM_MEI && !(z + p[8] * n > 0.0f)) return false;
+      if ((a.flags & UD_SPLAT_FOV) && !(z >= cos_limit * n)) return false;
+    }
+    ud_cam_project(m, p, x, y, z, &u, &v);
+    dep = ud_cam_depth(m, x, y, z);
+    return true;
+  }
+};
+
+template <bool ROWS, class PROJ>
+__global__ __launch_bounds__(SP_THREADS) void sp_splat_kernel(SpArgs a, const PROJ proj) {
   const int tid = threadIdx.x;
   const long long first = (long long)blockIdx.x * SP_CHUNK;
   const bool packed = a.offsets != nullptr;
@@ -102,12 +141,11 @@ __global__ __launch_bounds__(SP_THREADS) void sp_splat_kernel(SpArgs a) {
       const float zt = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
       x = xt; y = yt; z = zt;
     }
-    const float* k = a.K + (a.nK == 1 ? 0 : (size_t)b * 9);
-    const float pa = (k[0] * x + k[1] * y) + k[2] * z;
-    const float pb = (k[3] * x + k[4] * y) + k[5] * z;
-    const float pw = (k[6] * x + k[7] * y) + k[8] * z;
-    const float u = pa / pw + a.pixel_offset;
-    const float v = pb / pw + a.pixel_offset;
+    float u, v, dep;
+    if (!proj(a, b, x, y, z, u, v, dep)) continue;
+    z = dep;                                               // from here on the point's depth
+    u = u + a.pixel_offset;
+    v = v + a.pixel_offset;
     const int cx = sp_cell(u, a.W, trunc_mode), cy = sp_cell(v, a.H, trunc_mode);
     if (cx < 0 || cy < 0) continue;
     if ((a.flags & UD_SPLAT_RANGE) && !(z >= a.dmin && z <= a.dmax)) continue;
@@ -190,69 +228,135 @@ extern "C" long long ud_splat_work_bytes(int B, int H, int W) {
   return (long long)B * H * W * 12;
 }
 
+namespace {
+
+// the checks ud_splat and ud_splat_camera share, in two halves around the projector's own (sp_check_rest_and_fill also fills the SpArgs of the call).  `fn` names
+// the entry point in the message; max_b and allowed_flags are the entry point's.
+template <class D>
+int sp_check_head(const D& d, const char* fn, int max_b, int allowed_flags) {
+  char msg[256];
+  if (!sp_sizes_ok(d.B, d.H, d.W) || d.B > max_b || d.n_points < 0 || d.n_points > 0x7fffffffLL) {
+    snprintf(msg, sizeof(msg), "%s: bad sizes (1 <= B <= %d, H, W >= 1, H*W < 2^31, 0 <= n_points < 2^31)", fn, max_b);
+    ud_set_error(msg);
+    return UD_ERR_BAD_ARG;
+  }
+  if (d.mode != UD_SPLAT_NEAREST && d.mode != UD_SPLAT_MEAN) {
+    snprintf(msg, sizeof(msg), "%s: unknown mode (UD_SPLAT_NEAREST or UD_SPLAT_MEAN)", fn);
+    ud_set_error(msg);
+    return UD_ERR_BAD_ARG;
+  }
+  if (d.flags & ~allowed_flags) {
+    snprintf(msg, sizeof(msg), "%s: unknown flag", fn);
+    ud_set_error(msg);
+    return UD_ERR_BAD_ARG;
+  }
+  if (!d.xyz || !d.depth || d.point_stride < 1 || d.comp_stride < 1 || d.batch_stride < 0) {
+    snprintf(msg, sizeof(msg), "%s: null pointer (xyz, depth), or bad strides (point_stride, comp_stride >= 1, batch_stride >= 0)", fn);
+    ud_set_error(msg);
+    return UD_ERR_BAD_ARG;
+  }
+  return UD_OK;
+}
+
+template <class D>
+int sp_check_rest_and_fill(const D& d, const char* fn, SpArgs& a) {
+  char msg[256];
+  if (d.T && d.nT != 1 && d.nT != d.B) {
+    snprintf(msg, sizeof(msg), "%s: nT must be 1 or B when T is given", fn);
+    ud_set_error(msg);
+    return UD_ERR_BAD_ARG;
+  }
+  if ((d.color != nullptr) != (d.rgb != nullptr)) {
+    snprintf(msg, sizeof(msg), "%s: color and rgb go together (a colour source and the image that receives it)", fn);
+    ud_set_error(msg);
+    return UD_ERR_BAD_ARG;
+  }
+  if (d.mode == UD_SPLAT_MEAN && (d.index || d.rgb)) {
+    snprintf(msg, sizeof(msg), "%s: index and rgb are outputs of UD_SPLAT_NEAREST only", fn);
+    ud_set_error(msg);
+    return UD_ERR_BAD_ARG;
+  }
+  const bool counts = d.mode == UD_SPLAT_MEAN || d.count;
+  const long long pixels = (long long)d.B * d.H * d.W;
+  if (!d.work || ((uintptr_t)d.work & 7) || d.work_bytes < pixels * (counts ? 12 : 8)) {
+    snprintf(msg, sizeof(msg), "%s: work is null, not 8-byte aligned, or smaller than 8 B per pixel (12 B with counts; ud_splat_work_bytes() covers both)", fn);
+    ud_set_error(msg);
+    return UD_ERR_BAD_ARG;
+  }
+  a.xyz = d.xyz; a.offsets = d.offsets; a.K = nullptr; a.T = d.T; a.color = d.color;
+  a.depth = d.depth; a.index = d.index; a.rgb = d.rgb; a.count = d.count;
+  a.words = (unsigned long long*)d.work;
+  a.counts = counts ? (unsigned*)((char*)d.work + pixels * 8) : nullptr;
+  a.bs = d.batch_stride; a.ps = d.point_stride; a.cs = d.comp_stride; a.n = d.n_points;
+  a.B = d.B; a.H = d.H; a.W = d.W; a.HW = d.H * d.W; a.nK = 0; a.nT = d.nT; a.mode = d.mode; a.flags = d.flags; a.color_f32 = d.color_f32;
+  a.pixel_offset = d.pixel_offset; a.dmin = d.dmin; a.dmax = d.dmax;
+  return UD_OK;
+}
+
+// fill, splat (one thread per point through `proj`), resolve
+template <class PROJ>
+int sp_launch(const SpArgs& a, const PROJ& proj, void* stream, const char* what) {
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 pix((unsigned)(((long long)a.HW + SP_RTILE - 1) / SP_RTILE), (unsigned)a.B);
+  hipLaunchKernelGGL(sp_fill_kernel, pix, dim3(SP_RTILE), 0, s, a);
+  if (a.n > 0) {
+    const dim3 grid((unsigned)((a.n + SP_CHUNK - 1) / SP_CHUNK), a.offsets ? 1u : (unsigned)a.B);
+    if (a.cs == 1) hipLaunchKernelGGL((sp_splat_kernel<true, PROJ>), grid, dim3(SP_THREADS), 0, s, a, proj);
+    else hipLaunchKernelGGL((sp_splat_kernel<false, PROJ>), grid, dim3(SP_THREADS), 0, s, a, proj);
+  }
+  hipLaunchKernelGGL(sp_resolve_kernel, pix, dim3(SP_RTILE), 0, s, a);
+  UD_CHECK_LAUNCH(what);
+  return UD_OK;
+}
+
+}  // namespace
+
 extern "C" int ud_splat(const UdSplat* desc, void* stream) {
   if (!desc) {
     ud_set_error("ud_splat: null descriptor");
     return UD_ERR_BAD_ARG;
   }
   const UdSplat& d = *desc;
-  if (!sp_sizes_ok(d.B, d.H, d.W) || d.n_points < 0 || d.n_points > 0x7fffffffLL) {
-    ud_set_error("ud_splat: bad sizes (1 <= B <= 65535, H, W >= 1, H*W < 2^31, 0 <= n_points < 2^31)");
-    return UD_ERR_BAD_ARG;
-  }
-  if (d.mode != UD_SPLAT_NEAREST && d.mode != UD_SPLAT_MEAN) {
-    ud_set_error("ud_splat: unknown mode (UD_SPLAT_NEAREST or UD_SPLAT_MEAN)");
-    return UD_ERR_BAD_ARG;
-  }
-  if (d.flags & ~(UD_SPLAT_TRUNC | UD_SPLAT_RANGE)) {
-    ud_set_error("ud_splat: unknown flag");
-    return UD_ERR_BAD_ARG;
-  }
-  if (!d.xyz || !d.depth || d.point_stride < 1 || d.comp_stride < 1 || d.batch_stride < 0) {
-    ud_set_error("ud_splat: null pointer (xyz, depth), or bad strides (point_stride, comp_stride >= 1, batch_stride >= 0)");
-    return UD_ERR_BAD_ARG;
-  }
+  SpArgs a;
+  int rc = sp_check_head(d, "ud_splat", 65535, UD_SPLAT_TRUNC | UD_SPLAT_RANGE);
+  if (rc != UD_OK) return rc;
   if (!d.K || (d.nK != 1 && d.nK != d.B)) {
     ud_set_error("ud_splat: K [nK,3,3] is required, nK = 1 or B");
     return UD_ERR_BAD_ARG;
   }
-  if (d.T && d.nT != 1 && d.nT != d.B) {
-    ud_set_error("ud_splat: nT must be 1 or B when T is given");
+  rc = sp_check_rest_and_fill(d, "ud_splat", a);
+  if (rc != UD_OK) return rc;
+  a.K = d.K; a.nK = d.nK;
+  return sp_launch(a, SpProjMatrix(), stream, "ud_splat launch");
+}
+
+extern "C" int ud_splat_camera(const UdSplatCamera* desc, void* stream) {
+  if (!desc) {
+    ud_set_error("ud_splat_camera: null descriptor");
     return UD_ERR_BAD_ARG;
   }
-  if ((d.color != nullptr) != (d.rgb != nullptr)) {
-    ud_set_error("ud_splat: color and rgb go together (a colour source and the image that receives it)");
-    return UD_ERR_BAD_ARG;
-  }
-  if (d.mode == UD_SPLAT_MEAN && (d.index || d.rgb)) {
-    ud_set_error("ud_splat: index and rgb are outputs of UD_SPLAT_NEAREST only");
-    return UD_ERR_BAD_ARG;
-  }
-  const bool counts = d.mode == UD_SPLAT_MEAN || d.count;
-  const long long pixels = (long long)d.B * d.H * d.W;
-  if (!d.work || ((uintptr_t)d.work & 7) || d.work_bytes < pixels * (counts ? 12 : 8)) {
-    ud_set_error("ud_splat: work is null, not 8-byte aligned, or smaller than 8 B per pixel (12 B with counts; ud_splat_work_bytes() covers both)");
-    return UD_ERR_BAD_ARG;
-  }
+  const UdSplatCamera& d = *desc;
   SpArgs a;
-  a.xyz = d.xyz; a.offsets = d.offsets; a.K = d.K; a.T = d.T; a.color = d.color;
-  a.depth = d.depth; a.index = d.index; a.rgb = d.rgb; a.count = d.count;
-  a.words = (unsigned long long*)d.work;
-  a.counts = counts ? (unsigned*)((char*)d.work + pixels * 8) : nullptr;
-  a.bs = d.batch_stride; a.ps = d.point_stride; a.cs = d.comp_stride; a.n = d.n_points;
-  a.B = d.B; a.H = d.H; a.W = d.W; a.HW = d.H * d.W; a.nK = d.nK; a.nT = d.nT; a.mode = d.mode; a.flags = d.flags; a.color_f32 = d.color_f32;
-  a.pixel_offset = d.pixel_offset; a.dmin = d.dmin; a.dmax = d.dmax;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 pix((unsigned)(((long long)a.HW + SP_RTILE - 1) / SP_RTILE), (unsigned)d.B);
-  hipLaunchKernelGGL(sp_fill_kernel, pix, dim3(SP_RTILE), 0, s, a);
-  if (d.n_points > 0) {
-    const dim3 grid((unsigned)((d.n_points + SP_CHUNK - 1) / SP_CHUNK), d.offsets ? 1u : (unsigned)d.B);
-    if (d.comp_stride == 1) hipLaunchKernelGGL(sp_splat_kernel<true>, grid, dim3(SP_THREADS), 0, s, a);
-    else hipLaunchKernelGGL(sp_splat_kernel<false>, grid, dim3(SP_THREADS), 0, s, a);
+  int rc = sp_check_head(d, "ud_splat_camera", UD_RECON_MAX_B, UD_SPLAT_TRUNC | UD_SPLAT_RANGE | UD_SPLAT_FOV);
+  if (rc != UD_OK) return rc;
+  if (!d.params) {
+    ud_set_error("ud_splat_camera: params [B,16] is required");
+    return UD_ERR_BAD_ARG;
   }
-  hipLaunchKernelGGL(sp_resolve_kernel, pix, dim3(SP_RTILE), 0, s, a);
-  UD_CHECK_LAUNCH("ud_splat launch");
-  return UD_OK;
+  SpProjCamera proj;
+  proj.params = d.params; proj.cos_limit = d.cos_limit;
+  for (int b = 0; b < UD_RECON_MAX_B; ++b) proj.model[b] = 0;
+  for (int b = 0; b < d.B; ++b) {
+    const int m = d.model[b];
+    if (m < UD_CAM_PINHOLE || m > UD_CAM_MEI) {
+      ud_set_error("ud_splat_camera: model tag outside 1..6");
+      return UD_ERR_BAD_ARG;
+    }
+    proj.model[b] = (unsigned char)m;
+  }
+  rc = sp_check_rest_and_fill(d, "ud_splat_camera", a);
+  if (rc != UD_OK) return rc;
+  return sp_launch(a, proj, stream, "ud_splat_camera launch");
 }
 
 extern "C" int ud_depth_minpool(const UdDepthMinPool* desc, void* stream) {

@@ -1,14 +1,18 @@
-"""Point clouds back into images, over ud_splat / ud_depth_minpool (include/unidepth_hip.h UdSplat, UdDepthMinPool; csrc/splat.hip):
+"""Point clouds back into images, over ud_splat / ud_splat_camera / ud_camera_project / ud_depth_minpool (include/unidepth_hip.h UdSplat,
+UdSplatCamera, UdCameraProject, UdDepthMinPool; csrc/splat.hip, csrc/project.hip):
 
     render_depth, RenderedView      a batch of clouds (planar point maps, [B,N,3] rows or a packed PointCloud) splatted into depth maps
                                     through pinhole intrinsics and an optional rigid transform: z-buffer (nearest) or mean depth
     reproject                       render_depth on an infer() dict's `points`
+    render_depth_camera             render_depth through any of the six camera models (one per image) instead of a pinhole matrix
+    project_camera                  Camera.project for a batch: image coordinates, the in-image test and the model's depth, one launch
     project_points, downsample      unidepth/utils/geometric.py:161-204, 208-224 (same names, arguments and result shapes)
 
 Three launches for the whole batch (fill, splat, resolve), integer atomics only: bitwise reproducible, stream-ordered, and without any
 host synchronisation.  Tensors must live on the GPU: there is no CPU path."""
 from __future__ import annotations
 
+import math
 import sys
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -47,31 +51,11 @@ def _image_shape(fn, image_shape):
     return H, W
 
 
-def render_depth(points, intrinsics: torch.Tensor, image_shape: Tuple[int, int], *, transform: Optional[torch.Tensor] = None,
-                 image: Optional[torch.Tensor] = None, mode: str = "nearest", pixel_offset: float = 0.0, rounding: str = "floor",
-                 depth_range=None, return_index: bool = False, return_count: bool = False,
-                 workspace: Optional[torch.Tensor] = None) -> RenderedView:
-    """Splat a batch of point clouds into (H, W) = image_shape depth maps.
-
-    points: fp32 [B,3,h,w] (infer()'s planar point map), fp32 [B,N,3] (the reference's rows), or a PointCloud (packed rows of a batch;
-    its device offsets say which image a row belongs to and are never read on the host).  intrinsics fp32 [3,3], [1,3,3] or [B,3,3]: the
-    full matrix is applied, (a, b, w) = K (x, y, z), u = a / w + pixel_offset, v = b / w + pixel_offset.  transform fp32 [3,4] / [4,4]
-    (or [1,..] / [B,..]): a rigid motion applied to the points first (source camera -> destination camera).  All in fp32, every
-    operation rounded separately.
-
-    pixel_offset: the continuous coordinate u covers pixel floor(u).  Use 0.5 for clouds unprojected at INTEGER pixel centres
-    (pack_points in depth mode, get_pointcloud_from_rgbd: x = (u - cx) d / fx with u = 0, 1, ...): their points project back to integer
-    coordinates give or take rounding, and the half pixel puts them in the middle of their own cell.  Use 0 for the reference's
-    project_points convention, and for clouds whose pixel centres already sit at half-integer coordinates (infer()'s rays).
-    rounding: "floor" (default), or "trunc" for the reference's .int(), which also takes u in (-1, 0) into column 0.
-
-    mode "nearest": a z-buffer; points with z <= 0 are dropped, the smallest z wins a pixel and, among equal z, the smallest point
-    index.  image (uint8 or fp32, shaped like the points: [B,3,h,w], [B,N,3], or [rows,3] for a PointCloud, where it defaults to the
-    cloud's rgb) gives `rgb`, the winners' colours; return_index their indices.  mode "mean": the reference's mean depth per pixel
-    (negative z allowed; an order-free fixed-point sum, exact to 2^-25 + one fp32 rounding); image and return_index are refused.
-    depth_range (min, max) keeps min <= z <= max.  return_count: the number of kept points per pixel.
-    workspace: an optional uint8 GPU tensor of at least ud_splat_work_bytes(B, H, W) bytes to reuse."""
-    fn = "render_depth"
+def _render(fn, points, image_shape, projector, transform, image, mode, pixel_offset, rounding, depth_range, return_index, return_count,
+            workspace, flags=0) -> RenderedView:
+    """What render_depth and render_depth_camera share: the parsing of every argument but the projector's, the workspace, the outputs and
+    the call.  projector(B, device) -> (descriptor class, entry point's name, {tensors of the projector}, {its other fields},
+    [(index, value) of the descriptor's model array])."""
     H, W = _image_shape(fn, image_shape)
     offsets = None
     if isinstance(points, PointCloud):
@@ -103,7 +87,8 @@ def render_depth(points, intrinsics: torch.Tensor, image_shape: Tuple[int, int],
         raise ValueError(f"{fn}: mode must be 'nearest' or 'mean', got {mode!r}")
     if rounding not in ("floor", "trunc"):
         raise ValueError(f"{fn}: rounding must be 'floor' or 'trunc', got {rounding!r}")
-    tensors = {"xyz": xyz, "K": _matrices(fn, "intrinsics", intrinsics, B, 3, 3)}
+    desc_cls, entry, proj_tensors, proj_fields, models = projector(B, xyz.device)
+    tensors = {"xyz": xyz, **proj_tensors}
     if offsets is not None:
         tensors["offsets"] = offsets
     nT = 0
@@ -120,7 +105,7 @@ def render_depth(points, intrinsics: torch.Tensor, image_shape: Tuple[int, int],
         tensors["color"] = image.contiguous()
     if return_index and mode == "mean":
         raise ValueError(f"{fn}: return_index needs mode='nearest'")
-    flags = _lib.UD_SPLAT_TRUNC if rounding == "trunc" else 0
+    flags |= _lib.UD_SPLAT_TRUNC if rounding == "trunc" else 0
     dmin = dmax = 0.0
     if depth_range is not None:
         try:
@@ -149,13 +134,146 @@ def render_depth(points, intrinsics: torch.Tensor, image_shape: Tuple[int, int],
         rgb = torch.empty(B, 3, H, W, device=dev, dtype=image.dtype) if image is not None else None
         index = torch.empty(B, H, W, device=dev, dtype=torch.int32) if return_index else None
         count = torch.empty(B, H, W, device=dev, dtype=torch.int32) if return_count else None
-        d = mk(_lib.UdSplat, depth=depth, rgb=rgb, index=index, count=count, work=workspace, work_bytes=workspace.numel(),
+        d = mk(desc_cls, depth=depth, rgb=rgb, index=index, count=count, work=workspace, work_bytes=workspace.numel(),
                batch_stride=strides[0], point_stride=strides[1], comp_stride=strides[2], n_points=n, B=B, H=H, W=W,
-               nK=tensors["K"].shape[0], nT=nT, mode=_lib.UD_SPLAT_MEAN if mode == "mean" else _lib.UD_SPLAT_NEAREST, flags=flags,
+               nT=nT, mode=_lib.UD_SPLAT_MEAN if mode == "mean" else _lib.UD_SPLAT_NEAREST, flags=flags,
                color_f32=int(image is not None and image.dtype == torch.float32), pixel_offset=float(pixel_offset), dmin=dmin, dmax=dmax,
-               **tensors)
-        check(_lib.lib.ud_splat(d, cur_stream()), "ud_splat")
+               **proj_fields, **tensors)
+        for b, m in models:
+            d.model[b] = m
+        check(getattr(_lib.lib, entry)(d, cur_stream()), entry)
     return RenderedView(depth, rgb, index, count)
+
+
+def render_depth(points, intrinsics: torch.Tensor, image_shape: Tuple[int, int], *, transform: Optional[torch.Tensor] = None,
+                 image: Optional[torch.Tensor] = None, mode: str = "nearest", pixel_offset: float = 0.0, rounding: str = "floor",
+                 depth_range=None, return_index: bool = False, return_count: bool = False,
+                 workspace: Optional[torch.Tensor] = None) -> RenderedView:
+    """Splat a batch of point clouds into (H, W) = image_shape depth maps.
+
+    points: fp32 [B,3,h,w] (infer()'s planar point map), fp32 [B,N,3] (the reference's rows), or a PointCloud (packed rows of a batch;
+    its device offsets say which image a row belongs to and are never read on the host).  intrinsics fp32 [3,3], [1,3,3] or [B,3,3]: the
+    full matrix is applied, (a, b, w) = K (x, y, z), u = a / w + pixel_offset, v = b / w + pixel_offset.  transform fp32 [3,4] / [4,4]
+    (or [1,..] / [B,..]): a rigid motion applied to the points first (source camera -> destination camera).  All in fp32, every
+    operation rounded separately.
+
+    pixel_offset: the continuous coordinate u covers pixel floor(u).  Use 0.5 for clouds unprojected at INTEGER pixel centres
+    (pack_points in depth mode, get_pointcloud_from_rgbd: x = (u - cx) d / fx with u = 0, 1, ...): their points project back to integer
+    coordinates give or take rounding, and the half pixel puts them in the middle of their own cell.  Use 0 for the reference's
+    project_points convention, and for clouds whose pixel centres already sit at half-integer coordinates (infer()'s rays).
+    rounding: "floor" (default), or "trunc" for the reference's .int(), which also takes u in (-1, 0) into column 0.
+
+    mode "nearest": a z-buffer; points with z <= 0 are dropped, the smallest z wins a pixel and, among equal z, the smallest point
+    index.  image (uint8 or fp32, shaped like the points: [B,3,h,w], [B,N,3], or [rows,3] for a PointCloud, where it defaults to the
+    cloud's rgb) gives `rgb`, the winners' colours; return_index their indices.  mode "mean": the reference's mean depth per pixel
+    (negative z allowed; an order-free fixed-point sum, exact to 2^-25 + one fp32 rounding); image and return_index are refused.
+    depth_range (min, max) keeps min <= z <= max.  return_count: the number of kept points per pixel.
+    workspace: an optional uint8 GPU tensor of at least ud_splat_work_bytes(B, H, W) bytes to reuse."""
+    fn = "render_depth"
+
+    def projector(B, dev):
+        K = _matrices(fn, "intrinsics", intrinsics, B, 3, 3)
+        return _lib.UdSplat, "ud_splat", {"K": K}, {"nK": K.shape[0]}, ()
+    return _render(fn, points, image_shape, projector, transform, image, mode, pixel_offset, rounding, depth_range, return_index,
+                   return_count, workspace)
+
+
+def _camera_rows(fn, camera, B, dev):
+    """prepare_camera for the projecting functions: a CPU batch is refused here, in this module's words."""
+    from .gtpoints import prepare_camera
+    if dev.type != "cuda":
+        raise ValueError(f"{fn}: points must live on the GPU; there is no CPU path")
+    cam = prepare_camera(camera, B, dev)
+    if cam.params.device != dev:
+        raise ValueError(f"{fn}: the prepared camera lives on {cam.params.device}, the points on {dev}")
+    return cam
+
+
+def render_depth_camera(points, camera, image_shape: Tuple[int, int], *, transform: Optional[torch.Tensor] = None,
+                        image: Optional[torch.Tensor] = None, mode: str = "nearest", pixel_offset: float = 0.0, rounding: str = "floor",
+                        depth_range=None, max_angle: Optional[float] = None, return_index: bool = False, return_count: bool = False,
+                        workspace: Optional[torch.Tensor] = None) -> RenderedView:
+    """render_depth through a camera MODEL instead of a pinhole matrix (ud_splat_camera): every argument but `camera` and `max_angle` as
+    in render_depth, the same three launches.  camera: anything gtpoints.prepare_camera takes -- an intrinsics tensor, a Pinhole / EUCM /
+    Spherical / OPENCV / Fisheye624 / MEI, a BatchCamera (every image through its own member), or a PreparedCamera (under graph capture
+    and in loops: nothing is copied from the host then).
+
+    A point lands on the pixel of (u, v) = Camera.project(point) + pixel_offset.  Its depth -- what the z-buffer compares, the mean
+    averages, depth_range tests and `depth` holds -- is the model's depth, the quantity gt_points multiplies with: z, or the distance
+    |xyz| for Spherical.  So render_depth_camera(gt_points(depth, cam), cam, (H, W)) returns `depth`.  Every model but Spherical drops
+    points with z <= 0, MEI those behind its mirror's horizon (z + xi |xyz| <= 0).  max_angle (radians): keep only points within that
+    angle of the optical axis (z >= cos(max_angle) |xyz|; the cosine is taken on the host).  The polynomial models (OPENCV, Fisheye624,
+    MEI) fold points far outside their field of view back into the image: this is how to cull them."""
+    fn = "render_depth_camera"
+    flags, cos_limit = 0, 0.0
+    if max_angle is not None:
+        try:
+            cos_limit = math.cos(float(max_angle))
+        except (TypeError, ValueError):
+            raise ValueError(f"{fn}: max_angle must be a number (radians)") from None
+        flags = _lib.UD_SPLAT_FOV
+
+    def projector(B, dev):
+        cam = _camera_rows(fn, camera, B, dev)
+        return _lib.UdSplatCamera, "ud_splat_camera", {"params": cam.params}, {"cos_limit": cos_limit}, tuple(enumerate(cam.models))
+    return _render(fn, points, image_shape, projector, transform, image, mode, pixel_offset, rounding, depth_range, return_index,
+                   return_count, workspace, flags)
+
+
+def project_camera(points: torch.Tensor, camera, image_shape: Optional[Tuple[int, int]] = None, transform: Optional[torch.Tensor] = None):
+    """Camera.project for a batch in one launch (ud_camera_project): points fp32 [B,3,h,w] or [B,N,3] on the GPU, camera as
+    render_depth_camera takes it, one model per image -> (uv, inside, depth):
+
+        uv      fp32 [B,2,h,w] / [B,N,2]   image coordinates (pixel centres at half-integers, as gt_points places them)
+        inside  bool [B,h,w] / [B,N]       the model's own in-image test against image_shape = (H, W), comparisons as in the reference:
+                                           Pinhole 0 <= u < W and 0 <= v < H; the others not (u < 0 or u > W or v < 0 or v > H), EUCM also
+                                           not z < 0.  A NaN coordinate therefore counts as inside for every model but Pinhole.
+        depth   fp32 [B,h,w] / [B,N]       the model's depth of the point: z, or |xyz| for Spherical
+
+    image_shape defaults to (h, w) of a planar input and is required for rows.  transform fp32 [3,4] / [4,4] (or [1,..] / [B,..]) is
+    applied to the points first.  Nothing synchronises; camera objects are uploaded with one small copy (capture with a PreparedCamera)."""
+    fn = "project_camera"
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32:
+        raise ValueError(f"{fn}: points must be an fp32 tensor")
+    if points.ndim == 4 and points.shape[1] == 3:
+        B, n = points.shape[0], points.shape[2] * points.shape[3]
+        strides, rows, tail = (3 * n, 1, n), 0, tuple(points.shape[2:])
+        if image_shape is None:
+            image_shape = tail
+    elif points.ndim == 3 and points.shape[2] == 3:
+        B, n = points.shape[0], points.shape[1]
+        strides, rows, tail = (3 * n, 3, 1), 1, (n,)
+        if image_shape is None:
+            raise ValueError(f"{fn}: image_shape is required for [B,N,3] points")
+    else:
+        raise ValueError(f"{fn}: points must be [B,3,h,w] or [B,N,3], got {tuple(points.shape)}")
+    H, W = _image_shape(fn, image_shape)
+    if B <= 0:
+        raise ValueError(f"{fn}: empty batch")
+    if n > 2 ** 31 - 1:
+        raise ValueError(f"{fn}: unsupported sizes B={B} points={n}")
+    dev = points.device
+    cam = _camera_rows(fn, camera, B, dev)
+    xyz = points.contiguous()
+    T, nT = None, 0
+    if transform is not None:
+        if isinstance(transform, torch.Tensor) and transform.shape[-2:] == (4, 4):
+            transform = transform[..., :3, :]
+        T = _matrices(fn, "transform", transform, B, 3, 4)
+        if T.device != dev:
+            raise ValueError(f"{fn}: T must live on the GPU of the points ({dev}); there is no CPU path")
+        nT = T.shape[0]
+    with torch.cuda.device(dev):
+        uv = torch.empty((B, n, 2) if rows else (B, 2) + tail, device=dev, dtype=torch.float32)
+        inside = torch.empty((B,) + tail, device=dev, dtype=torch.uint8)
+        depth = torch.empty((B,) + tail, device=dev, dtype=torch.float32)
+        if n:
+            d = mk(_lib.UdCameraProject, xyz=xyz, params=cam.params, T=T, uv=uv, inside=inside, depth=depth, batch_stride=strides[0],
+                   point_stride=strides[1], comp_stride=strides[2], n_points=n, B=B, H=H, W=W, nT=nT, uv_rows=rows)
+            for b, m in enumerate(cam.models):
+                d.model[b] = m
+            check(_lib.lib.ud_camera_project(d, cur_stream()), "ud_camera_project")
+    return uv, inside.view(torch.bool), depth
 
 
 def reproject(out, intrinsics: torch.Tensor, transform: Optional[torch.Tensor] = None, image_shape: Optional[Tuple[int, int]] = None,
