@@ -603,6 +603,54 @@ typedef struct UdCameraProject {
 } UdCameraProject;
 int ud_camera_project(const UdCameraProject* desc, void* stream);
 
+/* And back: the viewing ray at ANY image coordinate, the device form of Camera.unproject / get_rays / reconstruct (utils/camera.py:
+ * base :69-92, Pinhole :255-273, EUCM :307-328, Spherical :371-392, OPENCV :496-694, Fisheye624 :778-974, MEI :985-1082, BatchCamera
+ * :1167-1171), one camera model per image, one thread per point (csrc/unproject.hip; the arithmetic is csrc/camera_models.h
+ * ud_cam_unproject_*).  Stream-ordered, no host synchronisation.
+ *   uv fp32: coordinate c of point r of image b is at uv[b * batch_stride + r * point_stride + c * comp_stride] (ELEMENTS), as
+ *     UdCameraProject addresses xyz: planar [B,2,h,w] is (2hw, 1, hw), rows [B,N,2] are (2N, 2, 1); batch_stride = 0 is one coordinate
+ *     set shared by every image.  uv = NULL: the identity grid of the descriptor's H, W at pixel centres u + 0.5, v + 0.5 (nothing is
+ *     materialised; n_points must be H * W; the strides are not read).
+ *   params fp32 [B,16] and model[b] as UdReconstruct.  depth fp32 [B,n_points] (optional).
+ *   rays fp32, planar [B,3,n_points] (rays_rows = 0) or rows [B,n_points,3] (rays_rows != 0).  Every operation rounds separately, every
+ *   maximum lets a NaN through (`x < m ? m : x`).  With depth = NULL and normalize = 0 the class's own unproject value, NOT normalised:
+ *     Pinhole     r = ((u - cx) / fx, (v - cy) / fy, 1), no skew;  r / max(r.z, 1e-4).  r.z is NaN instead of 1 when an intrinsic or a
+ *                 coordinate is not finite, so the whole ray is NaN then, as the reference's matrix product gives it
+ *     EUCM        mx = (u - cx) / fx, my likewise, r2 = mx*mx + my*my, mz = (1 - beta alpha^2 r2) / (alpha sqrt(max(1 - (2 alpha - 1) beta r2,
+ *                 1e-5)) + (1 - alpha)), c = 1 / sqrt(mx*mx + my*my + mz*mz + 1e-5);  (c mx, c my, max(c mz, 1e-3))
+ *     Spherical   lon = (u - (Wp - 1) / 2) / (Wp - 1) * (2 hfov2) with the ROW's Wp, Hp, lat likewise; s = (cos lat sin lon, sin lat,
+ *                 cos lat cos lon);  s / max(|s|, 1e-5)
+ *     OPENCV, Fisheye624   (dx, dy, 1) of the solvers: 10 Newton iterations undoing tangential and thin-prism terms, the trust-region
+ *                 loop on theta (at most 10 iterations), th / r (tan(th) / r for Fisheye624) along (xr, yr)
+ *     MEI         (dx, dy, pz): 20 tangential and 20 radial Newton iterations, lifted with the mirror parameter xi; fully per point
+ *   normalize != 0: that value / max(|value|, 1e-4), Camera.get_rays.  With depth the class's reconstruct rule, the expressions of
+ *   ud_reconstruct (so the identity grid with a depth gives ud_reconstruct's bits):
+ *     Pinhole r / max(r.z, 1e-4) * max(d, 0);  Spherical r * d;  the others r / max(r.z, 1e-4) * max(d, 1e-4), r as above
+ *   normalize together with depth is refused.
+ *   valid uint8 [B,n_points] (optional): the reference's unprojection_mask.  Pinhole: z of the stored ray > 1e-4.  EUCM: r2 < (alpha < 0.5
+ *     ? 1e6 : 1 / (beta (2 alpha - 1))) and c mz > 1e-3, taken before the clamp.  Spherical, OPENCV, Fisheye624, MEI: 1 (no mask there).
+ *   A batch without an OPENCV / Fisheye624 member is one launch.  Otherwise two after the clear: in the first every point of such an image runs its own
+ *   10 trust-region steps in registers and each workgroup publishes the largest |residual| at theta_0 .. theta_10 (one atomicMax per
+ *   workgroup and iteration); the second reads the iteration at which the image's maximum first fell below 1e-3, redoes that many steps and writes.
+ *   Every image leaves the radial loop on the maximum over ITS OWN points, the points this call was given (the reference takes the maximum
+ *   over the tensor its unproject receives); the iterates of a point depend on that point alone, so the result is that of an init / step /
+ *   final launch sequence bit for bit, with no per-point state in memory.  The maxima are cleared by the call (a small launch of its own on
+ *   `stream`), so a captured graph can be replayed with changed uv.
+ *   work: device scratch, 16-byte aligned, of at least ud_camera_unproject_work_bytes(B, n_iterative) bytes (host-only query; -1 for
+ *   arguments outside the limits): 11 maxima per iterative image.  May be NULL when there is no OPENCV / Fisheye624 member.
+ *   Limits: 1 <= B <= UD_RECON_MAX_B, H, W >= 1, 0 <= n_points < 2^31 - 256, point_stride, comp_stride >= 1, batch_stride >= 0 (with uv).
+ *   Every refusal is returned before any HIP call.  Built with -ffp-contract=off. */
+typedef struct UdCameraUnproject {
+  const float* uv; const float* params; const float* depth;
+  float* rays; unsigned char* valid;
+  void* work; long long work_bytes;
+  long long batch_stride, point_stride, comp_stride, n_points;
+  int B, H, W, normalize, rays_rows;
+  unsigned char model[UD_RECON_MAX_B];
+} UdCameraUnproject;
+int ud_camera_unproject(const UdCameraUnproject* desc, void* stream);
+long long ud_camera_unproject_work_bytes(int B, int n_iterative);
+
 /* ---- output side: the valid pixels of a batch of predictions as packed point-cloud rows (csrc/pointcloud.hip) ----
  * The device form of the reference's get_pointcloud_from_rgbd (unidepth/utils/visualization.py:57-104: numpy, one image per call) for a
  * whole batch: an ordered, deterministic stream compaction in a few plain launches on `stream` (flag + count, scan, pack), no atomics,
@@ -902,7 +950,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29; 16, 19, 22, 24 and 26 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31; 16, 19, 22, 24, 26 and 30 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

@@ -13,7 +13,8 @@ _VISUALIZATION = ("colorize", "colorize_batch", "demo_panel", "image_grid", "sav
 _REPROJECT = ("RenderedView", "render_depth", "reproject", "project_points", "downsample", "render_depth_camera", "project_camera")
 _TESTPREP = ("TestGeometry", "test_geometry", "prepare_test_batch", "resize_aa", "original_image")
 _GTPOINTS = ("gt_points", "add_points", "prepare_camera")
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS]
+_UNPROJECT = ("unproject_camera", "get_rays")
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT]
 
 
 def __getattr__(name):
@@ -41,4 +42,7 @@ def __getattr__(name):
     if name in _GTPOINTS:                             # ground-truth point maps for the validation loop (gtpoints.py, csrc/reconstruct.hip)
         from . import gtpoints
         return getattr(gtpoints, name)
+    if name in _UNPROJECT:                            # rays at arbitrary image coordinates (unproject.py, csrc/unproject.hip)
+        from . import unproject
+        return getattr(unproject, name)
     raise AttributeError(name)

@@ -117,6 +117,12 @@ class UdCameraProject(C.Structure):
                 ("B", i32), ("H", i32), ("W", i32), ("nT", i32), ("uv_rows", i32), ("model", C.c_ubyte * UD_RECON_MAX_B)]
 
 
+class UdCameraUnproject(C.Structure):
+    _fields_ = [("uv", vp), ("params", vp), ("depth", vp), ("rays", vp), ("valid", vp), ("work", vp), ("work_bytes", i64),
+                ("batch_stride", i64), ("point_stride", i64), ("comp_stride", i64), ("n_points", i64),
+                ("B", i32), ("H", i32), ("W", i32), ("normalize", i32), ("rays_rows", i32), ("model", C.c_ubyte * UD_RECON_MAX_B)]
+
+
 UD_PC_MINCONF, UD_PC_RANGE, UD_PC_EDGE, UD_PC_FLIP_Y = 1, 2, 4, 8
 
 
@@ -308,6 +314,7 @@ def _load():
         "ud_splat": [P(UdSplat), vp],
         "ud_splat_camera": [P(UdSplatCamera), vp],
         "ud_camera_project": [P(UdCameraProject), vp],
+        "ud_camera_unproject": [P(UdCameraUnproject), vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
         "ud_program_run": [vp, i32, i32, vp],
@@ -330,14 +337,16 @@ def _load():
     lib.ud_eval_3d_work_bytes.restype = i64
     lib.ud_reconstruct_work_bytes.argtypes = [i32, i32, i32, i32]
     lib.ud_reconstruct_work_bytes.restype = i64
+    lib.ud_camera_unproject_work_bytes.argtypes = [i32, i32]
+    lib.ud_camera_unproject_work_bytes.restype = i64
     lib.ud_pointcloud_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_pointcloud_work_bytes.restype = i64
     lib.ud_colorize_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera]):
-        if st is None:                                  # indices 16, 19, 22, 24 and 26 are not assigned: the library answers -1
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject]):
+        if st is None:                                  # indices 16, 19, 22, 24, 26 and 30 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

@@ -15,6 +15,8 @@ Only what the infer() path needs is here: the bookkeeping that maps a camera of 
 reproduces the reference's Newton / trust-region solvers including the image-wide early exit of the radial loop).  Unlike the reference, infer() does not modify the camera object it is given.
 Camera.reconstruct(depth), on every class, is the ground-truth point map of the validation loop (gtpoints.py, csrc/reconstruct.hip).
 Camera.project(points) / get_projection_mask(), on every class, go the other way (reproject.project_camera, csrc/project.hip).
+Camera.unproject(uv) / get_rays(shapes), on every class, are the rays at arbitrary image coordinates and of the pixel grid
+(unproject.unproject_camera, csrc/unproject.hip); unproject remembers the reference's unprojection_mask.
 Objects of the reference's own classes are accepted as well (matched by class name and `.params`)."""
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ class Camera:
     gt_mode = 0
     n_params = 4
     projection_mask = None                            # the mask of the last project() call (get_projection_mask)
+    unprojection_mask = None                          # the mask of the last unproject() call, where the class sets one
 
     def __init__(self, params: torch.Tensor):
         params = torch.as_tensor(params, dtype=torch.float32)
@@ -72,6 +75,27 @@ class Camera:
     def _projection_mask(self, inside: torch.Tensor):
         return inside
 
+    def unproject(self, uv: torch.Tensor) -> torch.Tensor:
+        """The reference's Camera.unproject: image coordinates [B,2,H,W] (or [B,N,2]) on the GPU -> the class's own rays fp32 [B,3,H,W]
+        ([B,N,3]), not normalised, every image through its own camera (unproject.unproject_camera, csrc/unproject.hip).  A batch-1 uv
+        goes through every camera, as the reference's BatchCamera concatenates its members' results.  Sets self.unprojection_mask: bool
+        [B,1,H,W] ([B,N]) for Pinhole (z > 1e-4) and EUCM (the model's domain; the reference's lacks the channel axis), None for the
+        classes that set none; for a BatchCamera every image follows its member's rule (True for the members without one)."""
+        from .unproject import unproject_camera
+        if not isinstance(uv, torch.Tensor):
+            raise ValueError(f"{type(self).__name__}.unproject: uv must be a tensor")
+        rays, mask = unproject_camera(uv, self, return_mask=True)
+        self.unprojection_mask = self._unprojection_mask(mask)
+        return rays
+
+    def _unprojection_mask(self, mask: torch.Tensor):
+        return None
+
+    def get_rays(self, shapes) -> torch.Tensor:
+        """The reference's Camera.get_rays: shapes = (B, H, W) or (H, W) -> the normalised rays fp32 [B,3,H,W] of the pixel centres."""
+        from .unproject import get_rays
+        return get_rays(self, shapes)
+
     def get_projection_mask(self):
         """The mask of the last project() call, bool [B,1,H,W], with the reference's returns class by class:
 
@@ -98,10 +122,16 @@ class Pinhole(Camera):
     def _projection_mask(self, inside):
         return ~inside                                # the reference's inversion, see get_projection_mask
 
+    def _unprojection_mask(self, mask):
+        return mask
+
 
 class EUCM(Camera):
     gt_mode = GT_EUCM
     n_params = 6
+
+    def _unprojection_mask(self, mask):
+        return mask
 
 
 class Spherical(Camera):
@@ -175,6 +205,9 @@ class BatchCamera(Camera):
     def _projection_mask(self, inside):
         flip = torch.tensor([isinstance(c, Pinhole) for c in self.cameras]).to(inside.device)
         return inside ^ flip[:, None, None, None]
+
+    def _unprojection_mask(self, mask):
+        return mask
 
     def uniform(self):
         cls = type(self.cameras[0])

@@ -294,3 +294,128 @@ UD_CAM_FN bool ud_cam_inside(int model, float u, float v, float z, int H, int W)
   if (model == UD_CAM_EUCM) return !(u < 0.0f || u > w || v < 0.0f || v > h || z < 0.0f);
   return !(u < 0.0f || u > w || v < 0.0f || v > h);
 }
+
+// ---- the inverse models at ANY image coordinate: Camera.unproject of every class (camera.py: Pinhole :255-266, EUCM :307-328, Spherical
+// :371-386, OPENCV :496-694, Fisheye624 :778-974, MEI :985-1082) and the three forms a caller can ask of the result (unproject.hip; the
+// arithmetic of the closed-form models is reconstruct.hip's, expression by expression, so that the identity grid with a depth gives the
+// bits of ud_reconstruct).  Every operation rounds separately under -ffp-contract=off; tests/unproj_host compiles these for the host.
+
+// the closed-form inverse of the skew-free K BEFORE the division by max(z, 1e-4): one subtraction and one division per axis; z is 1, or
+// NaN when an intrinsic or a coordinate is not finite: the reference inverts the whole matrix and its last row [0 0 1] multiplies
+// (u, v, 1), so the division by z turns the whole ray into NaN there as well
+UD_CAM_FN void ud_cam_unproject_pinhole(const float* p, float u, float v, float* x, float* y, float* z) {
+  *x = (u - p[2]) / p[0];
+  *y = (v - p[3]) / p[1];
+  *z = ((0.0f * (p[0] + p[1] + p[2] + p[3]) + 0.0f * u) + 0.0f * v) + 1.0f;
+}
+
+// (c mx, c my, c mz) with z NOT yet clamped to 1e-3, and the reference's unprojection_mask (taken before the clamp)
+UD_CAM_FN bool ud_cam_unproject_eucm(const float* p, float u, float v, float* x, float* y, float* z) {
+  const float al = p[4], be = p[5];
+  const float mx = (u - p[2]) / p[0], my = (v - p[3]) / p[1];
+  const float r2 = mx * mx + my * my;
+  const float sv = 1.0f - (2.0f * al - 1.0f) * be * r2;
+  const float mz = (1.0f - be * (al * al) * r2) / (al * sqrtf(ud_cam_floor(sv, 1e-5f)) + (1.0f - al));
+  const float cf = 1.0f / sqrtf(mx * mx + my * my + mz * mz + 1e-5f);
+  *x = cf * mx; *y = cf * my; *z = cf * mz;
+  const float lim = al < 0.5f ? 1e6f : 1.0f / (be * (2.0f * al - 1.0f));
+  return r2 < lim && *z > 1e-3f;
+}
+
+// the unit-sphere direction of an equirectangular pixel, re-normalised with the 1e-5 floor
+UD_CAM_FN void ud_cam_unproject_spherical(const float* p, float u, float v, float* x, float* y, float* z) {
+  const float lon = (u - (p[4] - 1.0f) / 2.0f) / (p[4] - 1.0f) * (2.0f * p[6]);
+  const float lat = (v - (p[5] - 1.0f) / 2.0f) / (p[5] - 1.0f) * (2.0f * p[7]);
+  const float cl = cosf(lat);
+  const float sx = cl * sinf(lon), sy = sinf(lat), sz = cl * cosf(lon);
+  const float n = ud_cam_floor(sqrtf(sx * sx + sy * sy + sz * sz), 1e-5f);
+  *x = sx / n; *y = sy / n; *z = sz / n;
+}
+
+// OPENCV / Fisheye624, the part before the radial loop: the tangential / thin-prism Newton iterations and |xr, yr|
+UD_CAM_FN bool ud_cam_radial_front(const float* p, float u, float v, float* xr, float* yr, float* rnorm) {
+  const int use_tan = fabsf(p[10]) + fabsf(p[11]) > 1e-6f;
+  const int use_prism = fabsf(p[12]) + fabsf(p[13]) + fabsf(p[14]) + fabsf(p[15]) > 1e-6f;
+  const float ud = (u - p[2]) / p[0], vd = (v - p[3]) / p[1];
+  ud_cam_undistort_tanprism(ud, vd, p[10], p[11], p[12], p[13], p[14], p[15], use_tan, use_prism, (use_tan || use_prism) ? 10 : 0, *xr, *yr);
+  *rnorm = sqrtf(*xr * *xr + *yr * *yr);
+  return fabsf(p[4]) + fabsf(p[5]) + fabsf(p[6]) + fabsf(p[7]) + fabsf(p[8]) + fabsf(p[9]) > 1e-6f;      // use_radial
+}
+
+// the larger of two non-negative residuals; a NaN wins, so that `max < eps` is false as in the reference
+UD_CAM_FN float ud_cam_nanmax(float a, float b) { return (b > a || b != b) ? b : a; }
+
+// the number of trust-region iterations the reference runs on a point set whose largest |residual| at theta_it is maxima[it], it = 0..9:
+// it leaves the loop at the first look below UD_CAM_EPS (camera.py:624)
+UD_CAM_FN int ud_cam_radial_exit(const float* maxima) {
+  int k = 0;
+  while (k < 10 && !(maxima[k] < UD_CAM_EPS)) ++k;
+  return k;
+}
+
+// theta after `steps` trust-region iterations from theta_0 = rnorm with the trust radius 0.1: a point's iterates depend on that point alone
+UD_CAM_FN float ud_cam_radial_solve(const float* k, int nk, float rnorm, int steps) {
+  float th = rnorm, delta = 0.1f;
+  for (int it = 0; it < steps; ++it) ud_cam_radial_step(k, nk, rnorm, th, delta);
+  return th;
+}
+
+enum { UD_UNPROJ_RAW = 0, UD_UNPROJ_NORMALIZE = 1, UD_UNPROJ_DEPTH = 2 };
+
+// what goes out for a direction r = (x, y, z) of `model` (Pinhole: before its division; EUCM: z before its clamp):
+//   RAW        the class's own unproject value: Pinhole r / max(r.z, 1e-4), EUCM (x, y, max(z, 1e-3)), the others r
+//   NORMALIZE  that / max(|that|, 1e-4): Camera.get_rays (camera.py:88-92)
+//   DEPTH      the class's reconstruct: Pinhole r / max(r.z, 1e-4) * max(d, 0); Spherical r * d; the others (EUCM after its clamp)
+//              r / max(r.z, 1e-4) * max(d, 1e-4)
+// Returns the reference's unprojection_mask where the class sets one (Pinhole: z of the stored ray > 1e-4), else true; EUCM's comes from
+// ud_cam_unproject_eucm.
+UD_CAM_FN bool ud_cam_unproject_form(int model, int form, float x, float y, float z, float d, float* o) {
+  bool valid = true;
+  if (model == UD_CAM_PINHOLE) {
+    const float zc = ud_cam_floor(z, 1e-4f);
+    valid = z / zc > 1e-4f;
+    if (form == UD_UNPROJ_DEPTH) {
+      const float dc = ud_cam_floor(d, 0.0f);
+      o[0] = x / zc * dc; o[1] = y / zc * dc; o[2] = z / zc * dc;
+      return valid;
+    }
+    x = x / zc; y = y / zc; z = z / zc;
+  } else if (model == UD_CAM_EUCM) {
+    z = ud_cam_floor(z, 1e-3f);
+  }
+  if (form == UD_UNPROJ_DEPTH) {
+    if (model == UD_CAM_SPHERICAL) {
+      o[0] = x * d; o[1] = y * d; o[2] = z * d;
+    } else {
+      const float zc = ud_cam_floor(z, 1e-4f), dc = ud_cam_floor(d, 1e-4f);
+      o[0] = x / zc * dc; o[1] = y / zc * dc; o[2] = z / zc * dc;
+    }
+  } else if (form == UD_UNPROJ_NORMALIZE) {
+    const float n = ud_cam_floor(sqrtf(x * x + y * y + z * z), 1e-4f);
+    o[0] = x / n; o[1] = y / n; o[2] = z / n;
+  } else {
+    o[0] = x; o[1] = y; o[2] = z;
+  }
+  return valid;
+}
+
+// a closed-form image's point, start to end (Pinhole, EUCM, Spherical, MEI)
+UD_CAM_FN bool ud_cam_unproject_closed(int model, int form, const float* p, float u, float v, float d, float* o) {
+  float x, y, z;
+  bool valid = true;
+  if (model == UD_CAM_PINHOLE) ud_cam_unproject_pinhole(p, u, v, &x, &y, &z);
+  else if (model == UD_CAM_EUCM) valid = ud_cam_unproject_eucm(p, u, v, &x, &y, &z);
+  else if (model == UD_CAM_SPHERICAL) ud_cam_unproject_spherical(p, u, v, &x, &y, &z);
+  else ud_cam_mei_dir(p, u, v, x, y, z);
+  const bool form_valid = ud_cam_unproject_form(model, form, x, y, z, d, o);
+  return valid && form_valid;
+}
+
+// an OPENCV / Fisheye624 point once the number of iterations of its image is known
+UD_CAM_FN void ud_cam_unproject_radial(int model, int form, const float* p, float u, float v, float d, int steps, float* o) {
+  float xr, yr, rnorm, dx, dy;
+  ud_cam_radial_front(p, u, v, &xr, &yr, &rnorm);
+  const float th = ud_cam_radial_solve(p + 4, model == UD_CAM_FISHEYE624 ? 6 : 3, rnorm, steps);
+  ud_cam_finish_radial_dir(xr, yr, rnorm, th, model == UD_CAM_FISHEYE624, dx, dy);
+  ud_cam_unproject_form(model, form, dx, dy, 1.0f, d, o);
+}
