@@ -651,6 +651,55 @@ typedef struct UdCameraUnproject {
 int ud_camera_unproject(const UdCameraUnproject* desc, void* stream);
 long long ud_camera_unproject_work_bytes(int B, int n_iterative);
 
+/* Sampling with such coordinates: the maps of a batch at arbitrary image coordinates in ONE launch (csrc/remap.hip; the arithmetic of a
+ * point is csrc/remap_taps.h).  A sampler and nothing else -- no camera arithmetic: the coordinates are ud_camera_project's uv of
+ * ud_camera_unproject's rays (undistortion, backward warping), keypoints, or anything else.  No workspace, no atomics, no host
+ * synchronisation: captures into a graph.
+ *   src  [B or 1 (src_shared != 0), C, Hs, Ws] planar, contiguous, fp32 or uint8 (src_u8 != 0), any C >= 1.
+ *   src_mask uint8 [B or 1 (mask_shared != 0), 1, Hs, Ws] (optional): a tap whose mask is 0 does not contribute.
+ *   uv fp32, addressed as UdCameraUnproject's: coordinate c of point r of image b at uv[b * batch_stride + r * point_stride + c * comp_stride]
+ *     (ELEMENTS); batch_stride = 0 shares one set.  Pixel centres at half-integers: the index-space position is x = u - 0.5, y = v - 0.5.
+ *   coord_valid uint8 [B,n_points] (optional; ud_camera_project's `inside`): a point with 0 gets value 0 and valid 0.
+ *   mode     UD_REMAP_NEAREST: the tap rint(x), rint(y), round half to even (grid_sample's nearbyint), the source's bits.
+ *            UD_REMAP_BILINEAR: taps floor(x), floor(x) + 1 and the same in y; lx = x - floor(x), hx = 1 - lx;
+ *              t0 = v00*hx + v01*lx, t1 = v10*hx + v11*lx, out = t0*hy + t1*ly, every operation rounded separately.
+ *   padding  UD_REMAP_ZEROS: a tap outside the source contributes 0 (grid_sample padding_mode="zeros", align_corners=False).
+ *            UD_REMAP_BORDER: x, y are clamped to [0, Ws - 1], [0, Hs - 1] first.
+ *   normalize != 0 (bilinear): the same expression over the contributing taps (in range, src_mask != 0) divided by the same expression
+ *     on 1 for those taps (their weight sum); 0 where that sum is 0.  The mode for depth maps with holes.
+ *   out  fp32, planar [B,C,n_points] (out_rows = 0) or rows [B,n_points,C] (out_rows != 0); or uint8 (out_u8 != 0, uint8 sources only):
+ *     rounded half to even and clamped to [0, 255].
+ *   valid uint8 [B,n_points] (optional): 1 only if coord_valid is 1, both coordinates are finite, 0 <= u <= Ws and 0 <= v <= Hs, and at
+ *     least one tap with a non-zero weight contributed.  A point whose coord_valid is 0 or whose coordinates are NaN or +-inf has out = 0
+ *     in every channel; a finite coordinate outside the image is sampled as the padding says (that is what grid_sample returns there)
+ *     with valid = 0.
+ *   A coordinate never becomes an address before it is safe: NaN, +-inf and huge values are clamped in floating point (NaN to a fixed
+ *   in-range value) before the conversion to an index.
+ *   Limits: 1 <= B <= UD_RECON_MAX_B, C, Hs, Ws, n_points >= 1; n_points, C * n_points, C * Hs * Ws < 2^31 - 256; point_stride,
+ *   comp_stride >= 1, batch_stride >= 0.  Every refusal is returned before any HIP call.  Built with -ffp-contract=off. */
+enum { UD_REMAP_NEAREST = 0, UD_REMAP_BILINEAR = 1 };  /* UdRemap.mode */
+enum { UD_REMAP_ZEROS = 0, UD_REMAP_BORDER = 1 };      /* UdRemap.padding */
+typedef struct UdRemap {
+  const void* src; const unsigned char* src_mask; const float* uv; const unsigned char* coord_valid;
+  void* out; unsigned char* valid;
+  long long batch_stride, point_stride, comp_stride, n_points;
+  int B, C, Hs, Ws, mode, padding, normalize, src_u8, out_u8, out_rows, src_shared, mask_shared;
+} UdRemap;
+int ud_remap(const UdRemap* desc, void* stream);
+
+/* The reference's Camera.mask_overlap_projection (utils/camera.py:132-154) for a batch in one launch: uv fp32 [B,2,H,W] (a projection of
+ * the pixel grid's own points) -> mask uint8 [B,1,H,W].  One thread per pixel; the flow uv - (x + 0.5, y + 0.5) is formed at the pixel
+ * and at each of the four taps, never stored.  Per pixel in fp32, every operation rounded separately: s = 0.1f * flow + id;
+ * g = s / (W - 1) * 2 - 1; ix = ((g + 1) * W - 1) / 2 (grid_sample, align_corners=False); clamp to [0, W - 1] (NaN to 0); floor; corner
+ * weights nw = (ix_se - ix) * (iy_se - iy), ...; sampled = nw v_nw + ne v_ne + sw v_sw + se v_se per component; norms sqrtf(a*a + b*b);
+ * mask = (0.9f |flow| < |sampled|) | (|flow| < 1).  A NaN makes both comparisons false.
+ * Limits: 1 <= B <= UD_RECON_MAX_B, H, W >= 2 (the reference divides by H - 1 and W - 1), H * W < 2^31 - 256. */
+typedef struct UdOverlapMask {
+  const float* uv; unsigned char* mask;
+  int B, H, W;
+} UdOverlapMask;
+int ud_overlap_mask(const UdOverlapMask* desc, void* stream);
+
 /* ---- output side: the valid pixels of a batch of predictions as packed point-cloud rows (csrc/pointcloud.hip) ----
  * The device form of the reference's get_pointcloud_from_rgbd (unidepth/utils/visualization.py:57-104: numpy, one image per call) for a
  * whole batch: an ordered, deterministic stream compaction in a few plain launches on `stream` (flag + count, scan, pack), no atomics,
@@ -950,7 +999,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31; 16, 19, 22, 24, 26 and 30 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34; 16, 19, 22, 24, 26, 30 and 32 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

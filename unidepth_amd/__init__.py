@@ -14,7 +14,8 @@ _REPROJECT = ("RenderedView", "render_depth", "reproject", "project_points", "do
 _TESTPREP = ("TestGeometry", "test_geometry", "prepare_test_batch", "resize_aa", "original_image")
 _GTPOINTS = ("gt_points", "add_points", "prepare_camera")
 _UNPROJECT = ("unproject_camera", "get_rays")
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT]
+_REMAP = ("remap", "undistort", "overlap_mask")
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP]
 
 
 def __getattr__(name):
@@ -45,4 +46,7 @@ def __getattr__(name):
     if name in _UNPROJECT:                            # rays at arbitrary image coordinates (unproject.py, csrc/unproject.hip)
         from . import unproject
         return getattr(unproject, name)
+    if name in _REMAP:                                # maps sampled at arbitrary image coordinates (remap.py, csrc/remap.hip)
+        import importlib                              # not `from . import remap`: that asks this function for "remap" first
+        return getattr(importlib.import_module(".remap", __name__), name)
     raise AttributeError(name)

@@ -123,6 +123,21 @@ class UdCameraUnproject(C.Structure):
                 ("B", i32), ("H", i32), ("W", i32), ("normalize", i32), ("rays_rows", i32), ("model", C.c_ubyte * UD_RECON_MAX_B)]
 
 
+UD_REMAP_NEAREST, UD_REMAP_BILINEAR = 0, 1
+UD_REMAP_ZEROS, UD_REMAP_BORDER = 0, 1
+
+
+class UdRemap(C.Structure):
+    _fields_ = [("src", vp), ("src_mask", vp), ("uv", vp), ("coord_valid", vp), ("out", vp), ("valid", vp),
+                ("batch_stride", i64), ("point_stride", i64), ("comp_stride", i64), ("n_points", i64),
+                ("B", i32), ("C", i32), ("Hs", i32), ("Ws", i32), ("mode", i32), ("padding", i32), ("normalize", i32), ("src_u8", i32),
+                ("out_u8", i32), ("out_rows", i32), ("src_shared", i32), ("mask_shared", i32)]
+
+
+class UdOverlapMask(C.Structure):
+    _fields_ = [("uv", vp), ("mask", vp), ("B", i32), ("H", i32), ("W", i32)]
+
+
 UD_PC_MINCONF, UD_PC_RANGE, UD_PC_EDGE, UD_PC_FLIP_Y = 1, 2, 4, 8
 
 
@@ -315,6 +330,8 @@ def _load():
         "ud_splat_camera": [P(UdSplatCamera), vp],
         "ud_camera_project": [P(UdCameraProject), vp],
         "ud_camera_unproject": [P(UdCameraUnproject), vp],
+        "ud_remap": [P(UdRemap), vp],
+        "ud_overlap_mask": [P(UdOverlapMask), vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
         "ud_program_run": [vp, i32, i32, vp],
@@ -345,8 +362,8 @@ def _load():
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject]):
-        if st is None:                                  # indices 16, 19, 22, 24, 26 and 30 are not assigned: the library answers -1
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask]):
+        if st is None:                                  # indices 16, 19, 22, 24, 26, 30 and 32 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

@@ -17,6 +17,8 @@ Camera.reconstruct(depth), on every class, is the ground-truth point map of the 
 Camera.project(points) / get_projection_mask(), on every class, go the other way (reproject.project_camera, csrc/project.hip).
 Camera.unproject(uv) / get_rays(shapes), on every class, are the rays at arbitrary image coordinates and of the pixel grid
 (unproject.unproject_camera, csrc/unproject.hip); unproject remembers the reference's unprojection_mask.
+Camera.get_overlap_mask() is the reference's mask_overlap_projection of the last project() call, for the two classes whose project sets
+it there, OPENCV and Fisheye624 (remap.overlap_mask, csrc/remap.hip).
 Objects of the reference's own classes are accepted as well (matched by class name and `.params`)."""
 from __future__ import annotations
 
@@ -30,6 +32,7 @@ class Camera:
     n_params = 4
     projection_mask = None                            # the mask of the last project() call (get_projection_mask)
     unprojection_mask = None                          # the mask of the last unproject() call, where the class sets one
+    overlap_mask = None                               # mask_overlap_projection of the last project() call, where the class sets one
 
     def __init__(self, params: torch.Tensor):
         params = torch.as_tensor(params, dtype=torch.float32)
@@ -62,7 +65,8 @@ class Camera:
     def project(self, points: torch.Tensor) -> torch.Tensor:
         """The reference's Camera.project: points fp32 [B,3,H,W] on the GPU -> image coordinates fp32 [B,2,H,W], every image through its
         own camera in one launch (reproject.project_camera, csrc/project.hip).  The image the mask is taken against is the point map's
-        own (H, W), as in the reference.  Remembers the mask of this call for get_projection_mask(); nothing else of the camera changes."""
+        own (H, W), as in the reference.  Remembers the mask of this call for get_projection_mask() and, for OPENCV and Fisheye624 (the
+        classes whose project sets it in the reference), the overlap mask of uv for get_overlap_mask(); nothing else of the camera changes."""
         from .reproject import project_camera
         if not isinstance(points, torch.Tensor) or points.ndim != 4 or points.shape[1] != 3:
             raise ValueError(f"{type(self).__name__}.project: points must be [B,3,H,W], got {tuple(getattr(points, 'shape', ()))}")
@@ -70,10 +74,14 @@ class Camera:
             raise RuntimeError(f"{type(self).__name__}.project: GPU tensors expected (the HIP kernels are the only implementation)")
         uv, inside, _ = project_camera(points, self)
         self.projection_mask = self._projection_mask(inside.unsqueeze(1))
+        self.overlap_mask = self._overlap_mask(uv)
         return uv
 
     def _projection_mask(self, inside: torch.Tensor):
         return inside
+
+    def _overlap_mask(self, uv: torch.Tensor):
+        return None
 
     def unproject(self, uv: torch.Tensor) -> torch.Tensor:
         """The reference's Camera.unproject: image coordinates [B,2,H,W] (or [B,N,2]) on the GPU -> the class's own rays fp32 [B,3,H,W]
@@ -108,6 +116,13 @@ class Camera:
 
         None before the first project()."""
         return self.projection_mask
+
+    def get_overlap_mask(self):
+        """The reference's mask_overlap_projection of the last project() call, bool [B,1,H,W] (remap.overlap_mask): False where the
+        projection folds content from another part of the image over the pixel.  OPENCV and Fisheye624 set it, as in the reference (MEI's
+        call is commented out there); None for Pinhole, EUCM, Spherical and MEI, and before the first project().  BatchCamera: with at
+        least one OPENCV / Fisheye624 member every image follows its member's rule (all True for the members without one), else None."""
+        return self.overlap_mask
 
 
 class Pinhole(Camera):
@@ -172,10 +187,18 @@ class OPENCV(_SingleCamera):
         super().__init__(params)
         assert float(self.params[..., 7:10].abs().sum()) == 0.0, "Do not support poly division model"   # utils/camera.py:416-418
 
+    def _overlap_mask(self, uv):
+        from .remap import overlap_mask
+        return overlap_mask(uv)
+
 
 class Fisheye624(_SingleCamera):
     gt_mode = GT_FISHEYE624
     n_params = 16
+
+    def _overlap_mask(self, uv):
+        from .remap import overlap_mask
+        return overlap_mask(uv)
 
 
 class MEI(_SingleCamera):
@@ -208,6 +231,13 @@ class BatchCamera(Camera):
 
     def _unprojection_mask(self, mask):
         return mask
+
+    def _overlap_mask(self, uv):
+        sets = [isinstance(c, (OPENCV, Fisheye624)) for c in self.cameras]
+        if not any(sets):
+            return None
+        from .remap import overlap_mask
+        return overlap_mask(uv) | ~torch.tensor(sets).to(uv.device)[:, None, None, None]
 
     def uniform(self):
         cls = type(self.cameras[0])

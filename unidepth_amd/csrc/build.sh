@@ -44,6 +44,9 @@ done
 ( hipcc $FLAGS -ffp-contract=off "$@" -c project.hip -o $BD/project.o ) & pids+=($!)
 # unproject: the inverse models of camera_models.h at arbitrary coordinates; the identity grid with a depth must give reconstruct's bits, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c unproject.hip -o $BD/unproject.o ) & pids+=($!)
+# remap: tap weights, the blend, the rounding to a byte and the overlap-mask decision are defined operation by operation in fp32 (remap_taps.h
+# under this flag is what the numpy fp32 restatement and the host build of the tests compute), same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c remap.hip -o $BD/remap.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)
