@@ -700,6 +700,49 @@ typedef struct UdOverlapMask {
 } UdOverlapMask;
 int ud_overlap_mask(const UdOverlapMask* desc, void* stream);
 
+/* Backward warping: ud_camera_unproject -> ud_camera_project -> ud_remap fused into ONE launch with one thread per destination pixel
+ * (csrc/warp.hip; the arithmetic of a pixel is csrc/warp_point.h, which only calls csrc/camera_models.h and csrc/remap_taps.h).  For every
+ * pixel of a destination view: its point, a rigid motion, the projection through the source camera, the source view's maps sampled there,
+ * the validity of the sample and an optional visibility test against the source's depth.  The point map, the coordinate map, the inside
+ * mask and the projected depth stay in registers; every output has the bits the separate calls give.  No workspace, no atomics, no LDS,
+ * no host synchronisation: captures into a graph.
+ *   The point of destination pixel i = y * Wo + x of image b, exactly one of:
+ *     points fp32 planar [B,3,Ho,Wo]: loaded (ud_reconstruct's or a network's point map).
+ *     depth  fp32 [B,Ho,Wo] with params_dst fp32 [B,16] and model_dst[b]: ud_camera_unproject's identity grid with a depth, the pixel
+ *            centre (x + 0.5, y + 0.5) through the model's reconstruct rule (Pinhole r / max(r.z, 1e-4) * max(d, 0); Spherical r * d;
+ *            EUCM, MEI r / max(r.z, 1e-4) * max(d, 1e-4)).  Closed-form destination models only (Pinhole, EUCM, Spherical, MEI): an
+ *            OPENCV / Fisheye624 member is REFUSED with UD_ERR_UNSUPPORTED -- its radial loop ends on a maximum over the whole image, so
+ *            the caller runs ud_camera_unproject and passes points.  model_dst and params_dst are not read in the points form.
+ *   T fp32 [nT,3,4] (nT = 1 or B; NULL = none): destination-camera to source-camera coordinates, ud_camera_project's arithmetic
+ *     (x' = ((t00*x + t01*y) + t02*z) + t03, ...).
+ *   params_src fp32 [B,16] and model_src[b] (all six models): (u, v) = ud_camera_project's coordinates of (x', y', z'), `inside` its
+ *     in-image test against Hs, Ws, dproj its depth (z', or |xyz'| for Spherical).
+ *   Coordinate validity cv = inside && dproj > 0, ANDed with valid_in[b,i] != 0 (uint8 [B,Ho,Wo], optional) and, in the depth form, with
+ *     depth > 0 (false for a NaN).  The destination model's unprojection mask (ud_camera_unproject's `valid`) is deliberately NOT part of
+ *     it, so both forms agree; pass it as valid_in where it is wanted.
+ *   src [B or 1 (src_shared != 0), C, Hs, Ws], src_mask uint8 [B or 1 (mask_shared != 0), 1, Hs, Ws] (optional), mode, padding, normalize,
+ *     src_u8, out_u8: UdRemap's, sampled at (u, v) with cv as its coord_valid.
+ *   out  fp32 or uint8 (out_u8 != 0, uint8 sources only), planar [B,C,Ho,Wo]: UdRemap's out.  0 in every channel where cv is 0 or a
+ *     coordinate is not finite.
+ *   valid uint8 [B,Ho,Wo] (optional): UdRemap's valid -- cv, both coordinates finite, 0 <= u <= Ws, 0 <= v <= Hs, a tap of non-zero weight.
+ *   visible uint8 [B,Ho,Wo] (optional; needs src_depth fp32 [B or 1 (depth_shared != 0), 1, Hs, Ws]): ds = src_depth sampled at the same
+ *     taps with the same mode and padding, a tap contributing only if its src_depth > 0 and its src_mask != 0, bilinear in the normalised
+ *     form; visible = (that sample is valid as above) && fabsf(ds - dproj) <= tol * dproj, every operation rounded separately, false for a
+ *     NaN.  tol_bits holds the bit pattern of the fp32 relative tolerance tol (the descriptor has integer and pointer fields only).
+ *   uv fp32 planar [B,2,Ho,Wo] (optional) and proj_depth fp32 [B,Ho,Wo] (optional): (u, v) and dproj of every pixel, valid or not.
+ *   A coordinate never becomes an address before it is safe (csrc/remap_taps.h).
+ *   Limits: 1 <= B <= UD_RECON_MAX_B, C, Ho, Wo, Hs, Ws >= 1; Ho * Wo, C * Ho * Wo, Hs * Ws, C * Hs * Ws < 2^31 - 256.  Every refusal is
+ *   returned before any HIP call.  Built with -ffp-contract=off. */
+typedef struct UdWarpCamera {
+  const void* src; const unsigned char* src_mask; const float* src_depth;
+  const float* points; const float* depth; const float* params_dst; const float* params_src; const float* T;
+  const unsigned char* valid_in;
+  void* out; unsigned char* valid; unsigned char* visible; float* uv; float* proj_depth;
+  int B, C, Ho, Wo, Hs, Ws, nT, mode, padding, normalize, src_u8, out_u8, src_shared, mask_shared, depth_shared, tol_bits;
+  unsigned char model_dst[UD_RECON_MAX_B], model_src[UD_RECON_MAX_B];
+} UdWarpCamera;
+int ud_warp_camera(const UdWarpCamera* desc, void* stream);
+
 /* ---- output side: the valid pixels of a batch of predictions as packed point-cloud rows (csrc/pointcloud.hip) ----
  * The device form of the reference's get_pointcloud_from_rgbd (unidepth/utils/visualization.py:57-104: numpy, one image per call) for a
  * whole batch: an ordered, deterministic stream compaction in a few plain launches on `stream` (flag + count, scan, pack), no atomics,
@@ -999,7 +1042,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34; 16, 19, 22, 24, 26, 30 and 32 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36; 16, 19, 22, 24, 26, 30, 32 and 35 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

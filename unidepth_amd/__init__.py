@@ -15,7 +15,8 @@ _TESTPREP = ("TestGeometry", "test_geometry", "prepare_test_batch", "resize_aa",
 _GTPOINTS = ("gt_points", "add_points", "prepare_camera")
 _UNPROJECT = ("unproject_camera", "get_rays")
 _REMAP = ("remap", "undistort", "overlap_mask")
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP]
+_WARP = ("warp_camera",)
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP, *_WARP]
 
 
 def __getattr__(name):
@@ -49,4 +50,7 @@ def __getattr__(name):
     if name in _REMAP:                                # maps sampled at arbitrary image coordinates (remap.py, csrc/remap.hip)
         import importlib                              # not `from . import remap`: that asks this function for "remap" first
         return getattr(importlib.import_module(".remap", __name__), name)
+    if name in _WARP:                                 # backward warping through the camera models in one launch (warp.py, csrc/warp.hip)
+        from . import warp
+        return getattr(warp, name)
     raise AttributeError(name)

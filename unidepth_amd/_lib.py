@@ -138,6 +138,14 @@ class UdOverlapMask(C.Structure):
     _fields_ = [("uv", vp), ("mask", vp), ("B", i32), ("H", i32), ("W", i32)]
 
 
+class UdWarpCamera(C.Structure):
+    _fields_ = [("src", vp), ("src_mask", vp), ("src_depth", vp), ("points", vp), ("depth", vp), ("params_dst", vp), ("params_src", vp),
+                ("T", vp), ("valid_in", vp), ("out", vp), ("valid", vp), ("visible", vp), ("uv", vp), ("proj_depth", vp),
+                ("B", i32), ("C", i32), ("Ho", i32), ("Wo", i32), ("Hs", i32), ("Ws", i32), ("nT", i32), ("mode", i32), ("padding", i32),
+                ("normalize", i32), ("src_u8", i32), ("out_u8", i32), ("src_shared", i32), ("mask_shared", i32), ("depth_shared", i32),
+                ("tol_bits", i32), ("model_dst", C.c_ubyte * UD_RECON_MAX_B), ("model_src", C.c_ubyte * UD_RECON_MAX_B)]
+
+
 UD_PC_MINCONF, UD_PC_RANGE, UD_PC_EDGE, UD_PC_FLIP_Y = 1, 2, 4, 8
 
 
@@ -332,6 +340,7 @@ def _load():
         "ud_camera_unproject": [P(UdCameraUnproject), vp],
         "ud_remap": [P(UdRemap), vp],
         "ud_overlap_mask": [P(UdOverlapMask), vp],
+        "ud_warp_camera": [P(UdWarpCamera), vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
         "ud_program_run": [vp, i32, i32, vp],
@@ -362,8 +371,8 @@ def _load():
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask]):
-        if st is None:                                  # indices 16, 19, 22, 24, 26, 30 and 32 are not assigned: the library answers -1
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera]):
+        if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32 and 35 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

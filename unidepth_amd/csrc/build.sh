@@ -47,6 +47,9 @@ done
 # remap: tap weights, the blend, the rounding to a byte and the overlap-mask decision are defined operation by operation in fp32 (remap_taps.h
 # under this flag is what the numpy fp32 restatement and the host build of the tests compute), same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c remap.hip -o $BD/remap.o ) & pids+=($!)
+# warp: unproject, project and remap fused per pixel (warp_point.h calls camera_models.h and remap_taps.h); each output must have the bits
+# of those launches run one after the other, same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c warp.hip -o $BD/warp.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)
