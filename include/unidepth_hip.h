@@ -474,6 +474,7 @@ int ud_rccl_finalize(void);
  *   dists fp32 [N,P1,K] squared L2 (norm 2) or L1 (norm 1) distances, idx int64 [N,P1,K]; every element is written (padding = 0).
  *   The K neighbours are the K smallest (dist, index) pairs in ascending order, i.e. already what functions/knn.py:75-91 obtains by
  *   sorting; ties resolve to the lower index (knn_cpu.cpp:40-58).  1 <= D <= 32 (D <= 8 on the register path), 1 <= K <= 32.
+ *   A slot whose distance is +inf (an inf coordinate, a square that overflows) reports index 0, with or without the P2 split.
  *   work: optional u64 [N*P1] scratch; when given and K == 1, small P1 problems are split over P2 (ud_knn_split slices). */
 typedef struct UdKnn {
   const float* p1; const float* p2;

@@ -134,6 +134,55 @@ def test_patch_extractor_matches_restatement(cfg):
         assert np.array_equal(out16.cpu().numpy(), re_.extract_patches(t.half().numpy(), c.half().numpy(), ps))
 
 
+def _edge_centers(H, W, ps, N):
+    """N centres (y, x) that leave the image: the four corners, one patch beyond each edge, far outside, negative and fractional ones
+    (the wrapper adds the padding in fp32, then truncates towards zero); the list repeats, shifted by one pixel, when N is larger."""
+    pw, ph = ps
+    base = [(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1), (-ph, W // 2), (H - 1 + ph, W // 2), (H // 2, -pw), (H // 2, W - 1 + pw),
+            (-40, W + 11), (H + 11, -40), (-0.5, 2.7), (2.7, -0.5), (-1, -1), (-2.3, W - 0.1), (H - 0.5, -1.5), (H // 2, W // 2), (-40, -40)]
+    out = [(y + k // len(base), x - k // len(base)) for k, (y, x) in zip(range(N), base * (N // len(base) + 1))]
+    return torch.tensor(out, dtype=torch.float32)
+
+
+# (B, C, H, W, N, (patch width, patch height)); B * N * C * h * w = 255, 256, 257 in the last three: the last block of 256 threads is
+# full but for one, full, and a single thread
+PATCH_EDGE_CASES = [(2, 2, 9, 11, 17, (4, 2)), (2, 3, 7, 5, 17, (3, 5)), (2, 2, 4, 3, 17, (7, 9)), (1, 1, 6, 7, 17, (5, 3)),
+                    (1, 2, 6, 7, 8, (4, 4)), (1, 1, 6, 7, 257, (1, 1))]
+
+
+@pytest.mark.parametrize("cfg", PATCH_EDGE_CASES)
+def test_patch_extractor_at_and_beyond_the_image_border(cfg):
+    """Centres on the corners, beyond every edge, far outside, negative and fractional; C = 2 and 3, even and odd sizes, patches larger
+    than the image, totals around one block: bit-exact against the restatement (zero outside the image), through the wrapper and
+    through the C-ABI with a guarded output and the image behind a NaN head."""
+    import ctypes as C
+    import layout_guard as lg
+    from unidepth_amd import _lib, eval_ops
+    from unidepth_amd.ops import cur_stream, mk
+    B, Cc, H, W, N, ps = cfg
+    pw, ph = ps
+    g = torch.Generator().manual_seed(H * 100 + W + N)
+    t = torch.randn(B, Cc, H, W, generator=g) + 3.0                    # no zeros inside the image: a zero in the result is padding
+    c = torch.stack([_edge_centers(H, W, ps, N).flip(0) if b % 2 else _edge_centers(H, W, ps, N) for b in range(B)])
+    ref = re_.extract_patches(t.numpy(), c.numpy(), ps)
+    total = B * N * Cc * ph * pw
+    assert ref.shape == (B, Cc, N, ph, pw) and ref.size == total
+    if N == 17:
+        assert (ref == 0).any() and (ref != 0).any()
+    out = eval_ops.RandomPatchExtractor()(t.cuda(), c.cuda(), ps)
+    assert out.shape == ref.shape and np.array_equal(out.cpu().numpy().view(np.int32), ref.view(np.int32))
+    head = 63
+    buf = lg._filled(head + t.numel(), torch.float32, lg.QNAN[torch.float32], "cuda")
+    buf[head:] = t.reshape(-1).cuda()
+    cpad = torch.from_numpy(np.trunc(c.numpy() + np.array([ph // 2, pw // 2], np.float32)).astype(np.int32)).cuda()
+    og = lg.guarded(1, total, total + 5, torch.float32, pre_rows=2, post_rows=2, offset_cols=3)
+    d = mk(_lib.UdExtractPatches, in_=buf[head:], out=og.ptr(), centers=cpad, B=B, C=Cc, H=H, W=W, N=N, h=ph, w=pw, pad_h=ph // 2, pad_w=pw // 2)
+    _lib.check(_lib.lib.ud_extract_patches(C.byref(d), cur_stream()), "ud_extract_patches")
+    torch.cuda.synchronize()
+    og.check_guards("out")
+    assert np.array_equal(og.view.cpu().numpy().reshape(-1).view(np.int32), ref.reshape(-1).view(np.int32))
+
+
 @pytest.mark.parametrize("name", mg.EVAL3D_CASES)
 def test_eval_3d_matches_reference_golden(golden_dir, name):
     """eval_3d (utils/evaluation_depth.py:160-182) end to end -- nearest-exact resampling to ~240 x 320 valid points, masked point

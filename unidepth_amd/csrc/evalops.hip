@@ -127,7 +127,8 @@ __global__ __launch_bounds__(256) void knn_kernel(const UdKnn p, const int span)
 
   if (q >= p.P1) return;
   if (gridDim.z > 1) {                 // K == 1 split: merge through the packed atomic (p.work pre-filled with ~0)
-    if (active && dk[0] < __builtin_inff()) {
+    // a slice that scanned a point always submits, also a winner at +inf (key 0x7f800000 << 32 < ~0): the slot must not stay "padding"
+    if (active && j_begin < j_end) {
       const unsigned long long key = ((unsigned long long)__float_as_uint(dk[0]) << 32) | (unsigned)ik[0];
       atomicMin(p.work + (size_t)n * p.P1 + q, key);
     }
@@ -223,7 +224,8 @@ __global__ __launch_bounds__(256) void knn1_d3_kernel(const UdKnn p, const int s
     if (q >= p.P1) continue;
     const size_t o = (size_t)n * p.P1 + q;
     if (split) {
-      if (act && b < __builtin_inff()) atomicMin(p.work + o, ((unsigned long long)__float_as_uint(b) << 32) | (unsigned)bi);
+      // as in knn_kernel: a slice that scanned a point submits its winner, (+inf, 0) included
+      if (act && j_begin < j_end) atomicMin(p.work + o, ((unsigned long long)__float_as_uint(b) << 32) | (unsigned)bi);
     } else {
       const bool ok = act && len2 > 0;
       p.dists[o] = ok ? b : 0.0f;
