@@ -744,6 +744,57 @@ typedef struct UdWarpCamera {
 } UdWarpCamera;
 int ud_warp_camera(const UdWarpCamera* desc, void* stream);
 
+/* Surface normals of a point map, or of a depth map seen through a camera, in ONE launch (csrc/normals.hip; the arithmetic of a pixel is
+ * csrc/normals_point.h, where the definition is written out operation by operation).  Exactly one of:
+ *     points fp32 planar [B,3,H,W]: the points form.  depth fp32 [B,H,W] is optional there and only feeds the edge test (P.z otherwise).
+ *     depth  fp32 [B,H,W] with params fp32 [B,16] and model[b] (points NULL): the depth form.  The point of a pixel is ud_reconstruct's at
+ *            the pixel centre, computed once per tile with a one-pixel halo and kept in LDS; ok additionally needs depth > 0.  Closed-form
+ *            models only (Pinhole, EUCM, Spherical, MEI): an OPENCV / Fisheye624 member is REFUSED with UD_ERR_UNSUPPORTED -- its radial
+ *            loop ends on a maximum over the whole image, so the caller runs ud_camera_unproject and passes points.
+ *   mask uint8 [B or 1 (mask_shared != 0), H, W] (optional): pixels with 0 are not ok.
+ *   A neighbour (left, right, up, down) is usable when it is inside the image, ok, and, with has_rtol != 0, |d[c] - d[q]| <= rtol *
+ *   min(d[c], d[q]) (rtol_bits holds the bit pattern of the fp32 rtol; false for a NaN).  dx = P[R] - P[L], or one-sided with P[c] when
+ *   only one of the two is usable; dy likewise with down and up; n = cross(dy, dx) / its largest magnitude, then / its length, negated
+ *   when n . P[c] > 0, so every valid normal faces the viewer.  A pixel is valid when it is ok, both differences exist and the largest
+ *   magnitude is > 0 and finite.
+ *   normals fp32 planar [B,3,H,W]: exactly 0 where not valid.  valid uint8 [B,H,W] (optional).  rgb uint8 planar [B,3,H,W] (optional):
+ *   floor((n + 1) * 127.5 + 0.5) clamped to 0..255, 0 where not valid.  No alignment is required of any pointer beyond its element's.
+ *   No workspace, no atomics, no host synchronisation: captures into a graph.
+ *   Limits: 1 <= B <= UD_RECON_MAX_B, H, W >= 1, H * W < 2^31 - 256, rtol finite and >= 0.  Every refusal is returned before any HIP
+ *   call.  Built with -ffp-contract=off. */
+typedef struct UdNormals {
+  const float* points; const float* depth; const float* params; const unsigned char* mask;
+  float* normals; unsigned char* valid; unsigned char* rgb;
+  int B, H, W, mask_shared, has_rtol, rtol_bits;
+  unsigned char model[UD_RECON_MAX_B];
+} UdNormals;
+int ud_normals(const UdNormals* desc, void* stream);
+
+/* Normal-error metrics of a batch, per image, without a host synchronisation (csrc/normals.hip).  Per pixel with mask != 0 and all six
+ * values finite: lg = sqrt((gx*gx + gy*gy) + gz*gz), lp likewise; dropped unless both are > 0 and finite; c = ((gx*px + gy*py) + gz*pz)
+ * / (lg * lp) clamped to [-1, 1] (a NaN quotient is dropped); the error is acosf(c).
+ *   gt, pred fp32 planar [B,3,H,W]; mask uint8 [B or 1 (mask_shared != 0), H, W] (optional).
+ *   out fp32 [3 + T, B]: mean, median, rmse in degrees, then for each threshold the share of pixels with c > cos_t, i.e. an error strictly
+ *     below it, as (float)count / (float)n.  cos_bits[t] holds the bit pattern of the fp32 rounding of the float64 cosine, computed by
+ *     the host.  NaN rows for an image without a usable pixel.
+ *   count int64 [B]: the usable pixels of each image.
+ *   error fp32 [B,H,W] (optional): (float)((double)acosf(c) * 180 / pi), NaN where dropped.
+ *   Sums are fp64 in a fixed order (thread, wave, block, chunk); only integer counts meet an atomic: two calls give the same bits.  The
+ *   median is the exact lower median of the error (torch.median): a radix select on the order-preserving keys of c for the rank
+ *   floor((n - 1) / 2) counted from the largest c, and one acosf.  workspace: at least ud_eval_normals_work_bytes(B, H, W, T) bytes
+ *   (host-only query; -1 outside the limits), 16-byte aligned; its contents on entry do not matter.
+ *   Limits: 1 <= B <= UD_RECON_MAX_B, H, W >= 1, H * W < 2^31 - 4096, 1 <= T <= UD_EVAL_NORMALS_MAX_T.  Every refusal is returned before
+ *   any HIP call.  Built with -ffp-contract=off. */
+#define UD_EVAL_NORMALS_MAX_T 8
+typedef struct UdEvalNormals {
+  const float* gt; const float* pred; const unsigned char* mask;
+  float* out; long long* count; float* error;
+  int B, H, W, T, mask_shared;
+  int cos_bits[UD_EVAL_NORMALS_MAX_T];
+} UdEvalNormals;
+int ud_eval_normals(const UdEvalNormals* desc, void* workspace, long long bytes, void* stream);
+long long ud_eval_normals_work_bytes(int B, int H, int W, int T);
+
 /* ---- output side: the valid pixels of a batch of predictions as packed point-cloud rows (csrc/pointcloud.hip) ----
  * The device form of the reference's get_pointcloud_from_rgbd (unidepth/utils/visualization.py:57-104: numpy, one image per call) for a
  * whole batch: an ordered, deterministic stream compaction in a few plain launches on `stream` (flag + count, scan, pack), no atomics,
@@ -1043,7 +1094,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36; 16, 19, 22, 24, 26, 30, 32 and 35 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39; 16, 19, 22, 24, 26, 30, 32, 35 and 37 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

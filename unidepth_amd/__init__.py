@@ -16,7 +16,8 @@ _GTPOINTS = ("gt_points", "add_points", "prepare_camera")
 _UNPROJECT = ("unproject_camera", "get_rays")
 _REMAP = ("remap", "undistort", "overlap_mask")
 _WARP = ("warp_camera",)
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP, *_WARP]
+_NORMALS = ("normals_from_points", "normals_camera", "eval_normals")
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP, *_WARP, *_NORMALS]
 
 
 def __getattr__(name):
@@ -53,4 +54,7 @@ def __getattr__(name):
     if name in _WARP:                                 # backward warping through the camera models in one launch (warp.py, csrc/warp.hip)
         from . import warp
         return getattr(warp, name)
+    if name in _NORMALS:                              # surface normals from points or depth, and their metrics (normals.py, csrc/normals.hip)
+        from . import normals
+        return getattr(normals, name)
     raise AttributeError(name)

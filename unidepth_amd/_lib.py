@@ -146,6 +146,20 @@ class UdWarpCamera(C.Structure):
                 ("tol_bits", i32), ("model_dst", C.c_ubyte * UD_RECON_MAX_B), ("model_src", C.c_ubyte * UD_RECON_MAX_B)]
 
 
+class UdNormals(C.Structure):
+    _fields_ = [("points", vp), ("depth", vp), ("params", vp), ("mask", vp), ("normals", vp), ("valid", vp), ("rgb", vp),
+                ("B", i32), ("H", i32), ("W", i32), ("mask_shared", i32), ("has_rtol", i32), ("rtol_bits", i32),
+                ("model", C.c_ubyte * UD_RECON_MAX_B)]
+
+
+UD_EVAL_NORMALS_MAX_T = 8
+
+
+class UdEvalNormals(C.Structure):
+    _fields_ = [("gt", vp), ("pred", vp), ("mask", vp), ("out", vp), ("count", vp), ("error", vp),
+                ("B", i32), ("H", i32), ("W", i32), ("T", i32), ("mask_shared", i32), ("cos_bits", i32 * UD_EVAL_NORMALS_MAX_T)]
+
+
 UD_PC_MINCONF, UD_PC_RANGE, UD_PC_EDGE, UD_PC_FLIP_Y = 1, 2, 4, 8
 
 
@@ -341,6 +355,8 @@ def _load():
         "ud_remap": [P(UdRemap), vp],
         "ud_overlap_mask": [P(UdOverlapMask), vp],
         "ud_warp_camera": [P(UdWarpCamera), vp],
+        "ud_normals": [P(UdNormals), vp],
+        "ud_eval_normals": [P(UdEvalNormals), vp, i64, vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
         "ud_program_run": [vp, i32, i32, vp],
@@ -361,6 +377,8 @@ def _load():
     lib.ud_eval_depth_work_bytes.restype = i64
     lib.ud_eval_3d_work_bytes.argtypes = [i32, i32, i32, i32]
     lib.ud_eval_3d_work_bytes.restype = i64
+    lib.ud_eval_normals_work_bytes.argtypes = [i32, i32, i32, i32]
+    lib.ud_eval_normals_work_bytes.restype = i64
     lib.ud_reconstruct_work_bytes.argtypes = [i32, i32, i32, i32]
     lib.ud_reconstruct_work_bytes.restype = i64
     lib.ud_camera_unproject_work_bytes.argtypes = [i32, i32]
@@ -371,8 +389,8 @@ def _load():
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera]):
-        if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32 and 35 are not assigned: the library answers -1
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals]):
+        if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35 and 37 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

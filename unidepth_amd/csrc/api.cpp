@@ -10,7 +10,7 @@ void ud_set_error(const char* msg) {
 }
 
 extern "C" const char* ud_last_error(void) { return g_err; }
-extern "C" int ud_version(void) { return 122; }
+extern "C" int ud_version(void) { return 123; }
 
 // struct sizes, so the Python binding can verify its ctypes mirror of include/unidepth_hip.h
 extern "C" int ud_struct_size(int which) {
@@ -44,6 +44,8 @@ extern "C" int ud_struct_size(int which) {
     case 33: return (int)sizeof(UdRemap);            // 32 stays unassigned (-1)
     case 34: return (int)sizeof(UdOverlapMask);
     case 36: return (int)sizeof(UdWarpCamera);       // 35 stays unassigned (-1)
+    case 38: return (int)sizeof(UdNormals);          // 37 stays unassigned (-1)
+    case 39: return (int)sizeof(UdEvalNormals);
     default: return -1;
   }
 }

@@ -50,6 +50,10 @@ done
 # warp: unproject, project and remap fused per pixel (warp_point.h calls camera_models.h and remap_taps.h); each output must have the bits
 # of those launches run one after the other, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c warp.hip -o $BD/warp.o ) & pids+=($!)
+# normals: the differences, the cross product, both normalisations, the orientation test and the byte rounding are defined operation by
+# operation in fp32 (normals_point.h under this flag is what the numpy fp32 restatement and the host build of the tests compute); the
+# depth form must have the bits of ud_reconstruct followed by the points form; the metric's cosine feeds exact threshold counts, same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c normals.hip -o $BD/normals.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)
