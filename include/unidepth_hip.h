@@ -744,6 +744,43 @@ typedef struct UdWarpCamera {
 } UdWarpCamera;
 int ud_warp_camera(const UdWarpCamera* desc, void* stream);
 
+/* Multi-view depth consistency and fusion in ONE launch (csrc/consistency.hip; the arithmetic of a pixel is csrc/consistency_point.h, which
+ * only calls csrc/camera_models.h and csrc/remap_taps.h): the forward-backward geometric filter of multi-view stereo for every pixel of a
+ * reference view against V neighbour views, one thread per reference pixel with the view loop inside it.  Per view it is ud_warp_camera ->
+ * ud_camera_unproject -> ud_camera_project and the element-wise comparisons fused; every output has the bits the separate calls give.  No
+ * workspace, no atomics, no LDS, no host synchronisation: captures into a graph.
+ *   Reference pixel i = y * W + x of image b: depth fp32 [B,H,W], params_ref fp32 [B,16], model_ref[b].  ref_ok = depth > 0 (false for a
+ *     NaN) && valid_in[b,i] != 0 (uint8 [B,H,W], optional).  P = ud_camera_unproject's identity grid with the depth at the pixel centre
+ *     (x + 0.5, y + 0.5), computed once.
+ *   View v = 0 .. V-1, in this order: src_depth fp32 [B,V,Hs,Ws], src_mask uint8 [B,V,Hs,Ws] (optional), params_src fp32 [V,B,16],
+ *     model_src[v * B + b]; T and Tinv fp32 [nT,V,3,4] (nT = 1 or B sets of V matrices): reference-camera to view-camera coordinates and
+ *     its inverse, ud_camera_project's arithmetic (x' = ((t00*x + t01*y) + t02*z) + t03, ...).
+ *       Q = T P; (u, v) = the view's projection of Q, dproj its depth; cv = ref_ok && inside(u, v; Hs, Ws) && dproj > 0.
+ *       ds = src_depth sampled at (u, v): bilinear, zeros padding, a tap contributing only if its depth > 0 and its src_mask != 0, the
+ *         normalised form -- UdWarpCamera's out and valid for src = src_depth[b,v], src_mask = (src_depth > 0) & src_mask, normalize = 1.
+ *       Q' = the view's reconstruct rule at (u, v) with ds; P' = Tinv Q'; (u', v') = the reference's projection of P', dback its depth.
+ *       e2 = (u' - (x + .5))^2 + (v' - (y + .5))^2; diff = fabsf(dback - depth);
+ *       consistent = valid sample && inside(u', v'; H, W) && dback > 0 && e2 <= px_tol * px_tol && diff <= rel_tol * depth, every
+ *         operation rounded separately in fp32, false whenever anything is a NaN.  A consistent view adds dback to a running sum that
+ *         starts at depth, in view order.
+ *   fused fp32 [B,H,W]: sum / (float)(count + 1), 0 where ref_ok is false.  count uint8 [B,H,W]: the consistent views.  mask uint8
+ *     [B,H,W]: ref_ok && count >= min_views.  Optional per-view maps [B,V,H,W]: consistent uint8, err_px fp32 (sqrtf(e2)), err_rel fp32
+ *     (diff / depth); the error maps are 0 where the sample is not valid.
+ *   px_tol_bits / rel_tol_bits hold the bit patterns of the fp32 tolerances (the descriptor has integer and pointer fields only).
+ *   Closed-form models only (Pinhole, EUCM, Spherical, MEI): an OPENCV / Fisheye624 member, reference or view, is REFUSED with
+ *   UD_ERR_UNSUPPORTED -- its unprojection ends on a maximum over the whole image.  A coordinate never becomes an address before it is
+ *   safe (csrc/remap_taps.h).
+ *   Limits: B, V >= 1, B * V <= UD_RECON_MAX_B, V <= 255, H, W, Hs, Ws >= 1; H * W, Hs * Ws, V * Hs * Ws < 2^31 - 256; nT 1 or B; px_tol,
+ *   rel_tol finite and >= 0; 0 <= min_views <= V.  Every refusal is returned before any HIP call.  Built with -ffp-contract=off. */
+typedef struct UdDepthConsistency {
+  const float* depth; const float* params_ref; const unsigned char* valid_in;
+  const float* src_depth; const unsigned char* src_mask; const float* params_src; const float* T; const float* Tinv;
+  float* fused; unsigned char* count; unsigned char* mask; unsigned char* consistent; float* err_px; float* err_rel;
+  int B, V, H, W, Hs, Ws, nT, min_views, px_tol_bits, rel_tol_bits;
+  unsigned char model_ref[UD_RECON_MAX_B], model_src[UD_RECON_MAX_B];
+} UdDepthConsistency;
+int ud_depth_consistency(const UdDepthConsistency* desc, void* stream);
+
 /* Surface normals of a point map, or of a depth map seen through a camera, in ONE launch (csrc/normals.hip; the arithmetic of a pixel is
  * csrc/normals_point.h, where the definition is written out operation by operation).  Exactly one of:
  *     points fp32 planar [B,3,H,W]: the points form.  depth fp32 [B,H,W] is optional there and only feeds the edge test (P.z otherwise).
@@ -1094,7 +1131,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39; 16, 19, 22, 24, 26, 30, 32, 35 and 37 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41; 16, 19, 22, 24, 26, 30, 32, 35, 37 and 40 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

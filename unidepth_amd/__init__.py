@@ -17,7 +17,9 @@ _UNPROJECT = ("unproject_camera", "get_rays")
 _REMAP = ("remap", "undistort", "overlap_mask")
 _WARP = ("warp_camera",)
 _NORMALS = ("normals_from_points", "normals_camera", "eval_normals")
-__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP, *_WARP, *_NORMALS]
+_CONSISTENCY = ("depth_consistency", "depth_consistency_composition", "invert_rigid")
+__all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP, *_WARP, *_NORMALS,
+           *_CONSISTENCY]
 
 
 def __getattr__(name):
@@ -57,4 +59,7 @@ def __getattr__(name):
     if name in _NORMALS:                              # surface normals from points or depth, and their metrics (normals.py, csrc/normals.hip)
         from . import normals
         return getattr(normals, name)
+    if name in _CONSISTENCY:                          # multi-view depth check and fusion in one launch (consistency.py, csrc/consistency.hip)
+        from . import consistency
+        return getattr(consistency, name)
     raise AttributeError(name)

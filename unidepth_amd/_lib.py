@@ -152,6 +152,13 @@ class UdNormals(C.Structure):
                 ("model", C.c_ubyte * UD_RECON_MAX_B)]
 
 
+class UdDepthConsistency(C.Structure):
+    _fields_ = [("depth", vp), ("params_ref", vp), ("valid_in", vp), ("src_depth", vp), ("src_mask", vp), ("params_src", vp), ("T", vp),
+                ("Tinv", vp), ("fused", vp), ("count", vp), ("mask", vp), ("consistent", vp), ("err_px", vp), ("err_rel", vp),
+                ("B", i32), ("V", i32), ("H", i32), ("W", i32), ("Hs", i32), ("Ws", i32), ("nT", i32), ("min_views", i32),
+                ("px_tol_bits", i32), ("rel_tol_bits", i32), ("model_ref", C.c_ubyte * UD_RECON_MAX_B), ("model_src", C.c_ubyte * UD_RECON_MAX_B)]
+
+
 UD_EVAL_NORMALS_MAX_T = 8
 
 
@@ -356,6 +363,7 @@ def _load():
         "ud_overlap_mask": [P(UdOverlapMask), vp],
         "ud_warp_camera": [P(UdWarpCamera), vp],
         "ud_normals": [P(UdNormals), vp],
+        "ud_depth_consistency": [P(UdDepthConsistency), vp],
         "ud_eval_normals": [P(UdEvalNormals), vp, i64, vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
@@ -389,8 +397,8 @@ def _load():
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals]):
-        if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35 and 37 are not assigned: the library answers -1
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency]):
+        if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35, 37 and 40 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

@@ -10,7 +10,7 @@ void ud_set_error(const char* msg) {
 }
 
 extern "C" const char* ud_last_error(void) { return g_err; }
-extern "C" int ud_version(void) { return 123; }
+extern "C" int ud_version(void) { return 124; }
 
 // struct sizes, so the Python binding can verify its ctypes mirror of include/unidepth_hip.h
 extern "C" int ud_struct_size(int which) {
@@ -46,6 +46,7 @@ extern "C" int ud_struct_size(int which) {
     case 36: return (int)sizeof(UdWarpCamera);       // 35 stays unassigned (-1)
     case 38: return (int)sizeof(UdNormals);          // 37 stays unassigned (-1)
     case 39: return (int)sizeof(UdEvalNormals);
+    case 41: return (int)sizeof(UdDepthConsistency); // 40 stays unassigned (-1)
     default: return -1;
   }
 }

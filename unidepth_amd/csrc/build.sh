@@ -54,6 +54,10 @@ done
 # operation in fp32 (normals_point.h under this flag is what the numpy fp32 restatement and the host build of the tests compute); the
 # depth form must have the bits of ud_reconstruct followed by the points form; the metric's cosine feeds exact threshold counts, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c normals.hip -o $BD/normals.o ) & pids+=($!)
+# consistency: warp, unproject, project and the comparisons of the forward-backward depth check fused per pixel over all views
+# (consistency_point.h calls camera_models.h and remap_taps.h); each output must have the bits of those launches run one after the other,
+# same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c consistency.hip -o $BD/consistency.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)
