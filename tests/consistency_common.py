@@ -4,13 +4,12 @@ and special values -- the call of the host program tests/consistency_host/consis
 the GPU tests.  The oracle of the GPU tests is unidepth_amd.consistency.depth_consistency_composition, the merged calls in a loop, never
 the fused kernel."""
 import functools
-import os
-import struct
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_program
+from host_program import ROOT, bits, f32_bits  # noqa: F401  (the tests reach them through this module)
+
 PINHOLE, EUCM, SPHERICAL, OPENCV, FISHEYE624, MEI = 1, 2, 3, 4, 5, 6
 NAMES = {PINHOLE: "pinhole", EUCM: "eucm", SPHERICAL: "spherical", MEI: "mei"}
 CLOSED = (PINHOLE, EUCM, SPHERICAL, MEI)
@@ -143,10 +142,6 @@ def assert_edge_shares(name, consistent):
         assert_shares(consistent, name)
 
 
-def f32_bits(x):
-    return struct.unpack("<i", struct.pack("<f", x))[0]
-
-
 def invert(T):
     """unidepth_amd.consistency.invert_rigid on a numpy array (plain torch, runs on the CPU)"""
     import torch
@@ -155,11 +150,7 @@ def invert(T):
 
 
 def build_host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("consistency_host") / "consistency_host")
-    # -ffp-contract=off: no fused multiply-adds, the rounding consistency.hip is built with
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", out,
-                           os.path.join(ROOT, "tests", "consistency_host", "consistency_host.cpp")])
-    return out
+    return host_program.build(tmp_path_factory, "consistency_host")
 
 
 def host_consistency(exe, depth, params_ref, models_ref, src_depths, params_src, models_src, T, *, px_tol=PX_TOL, rel_tol=REL_TOL, min_views=1,
@@ -177,15 +168,8 @@ def host_consistency(exe, depth, params_ref, models_ref, src_depths, params_src,
     blobs += [np.ascontiguousarray(valid_in, np.uint8).tobytes()] if valid_in is not None else []
     args = [B, V, H, W, Hs, Ws, Tn.shape[0], int(valid_in is not None), int(src_masks is not None), min_views, f32_bits(px_tol), f32_bits(rel_tol)]
     args += list(models_ref) + [models_src[v][b] for v in range(V) for b in range(B)]
-    p = subprocess.run([exe] + [str(a) for a in args], input=b"".join(blobs), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    assert p.returncode == 0, (p.returncode, p.stderr.decode()[-2000:])
     n = B * H * W
-    sizes = [4 * n, n, n, V * n, 4 * V * n, 4 * V * n]
-    assert len(p.stdout) == sum(sizes), (len(p.stdout), sizes)
-    parts, at = [], 0
-    for s in sizes:
-        parts.append(p.stdout[at:at + s])
-        at += s
+    parts = host_program.run(exe, args, blobs, [4 * n, n, n, V * n, 4 * V * n, 4 * V * n])
     return dict(fused=np.frombuffer(parts[0], np.float32).reshape(B, H, W), count=np.frombuffer(parts[1], np.uint8).reshape(B, H, W),
                 mask=np.frombuffer(parts[2], np.uint8).reshape(B, H, W).astype(bool),
                 consistent=np.frombuffer(parts[3], np.uint8).reshape(B, V, H, W).astype(bool),
@@ -301,24 +285,8 @@ def prepared(params, models):
     return gtpoints.PreparedCamera(torch.from_numpy(np.array(params, np.float32, order="C")).cuda(), models)
 
 
-def bits(t):
-    """a tensor as integers of its element width: NaN payloads and the sign of a zero count"""
-    import torch
-    t = t.contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.uint8) if t.dtype == torch.bool else t
-
-
 OUTPUTS = ("fused", "count", "mask", "consistent", "err_px", "err_rel")
 
 
 def assert_same(got, want, what="", names=OUTPUTS):
-    """every output, every element, bit for bit; the message says which output and how many elements"""
-    import torch
-    assert len(got) == len(want) == len(names), (what, len(got), len(want))
-    for name, a, b in zip(names, got, want):
-        assert a.dtype == b.dtype and a.shape == b.shape, (what, name, a.dtype, b.dtype, tuple(a.shape), tuple(b.shape))
-        if not torch.equal(bits(a), bits(b)):
-            diff = bits(a) != bits(b)
-            raise AssertionError(f"{what}: {name} differs in {int(diff.sum())} of {diff.numel()} elements, first at flat index "
-                                 f"{int(diff.reshape(-1).nonzero()[0])}: {a.reshape(-1)[diff.reshape(-1)][:4].tolist()} vs "
-                                 f"{b.reshape(-1)[diff.reshape(-1)][:4].tolist()}")
+    host_program.assert_same(got, want, names, what)

@@ -6,15 +6,13 @@ Every numpy operation below works on float32 arrays and rounds once, in the orde
 with an add."""
 import functools
 import math
-import os
-import struct
-import subprocess
 
 import numpy as np
 
+import host_program
 import warp_common as wc
+from host_program import ROOT, f32_bits, same_bits  # noqa: F401  (the tests reach them through this module)
 
-ROOT = wc.ROOT
 PINHOLE, EUCM, SPHERICAL, OPENCV, FISHEYE624, MEI = wc.PINHOLE, wc.EUCM, wc.SPHERICAL, wc.OPENCV, wc.FISHEYE624, wc.MEI
 CLOSED = wc.CLOSED
 H0, W0, B0 = 37, 53, 6
@@ -31,10 +29,6 @@ F32 = np.float32
 
 def rows(models):
     return wc.rows(models, wc.DST_ROWS)
-
-
-def f32_bits(v):
-    return struct.unpack("<i", struct.pack("<f", v))[0]
 
 
 # ---- the restatement of a normal ---------------------------------------------------------------------------------------------------
@@ -243,11 +237,7 @@ def check_known_answer(run):
 # ---- the host program ----------------------------------------------------------------------------------------------------------------
 
 def build_host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("normals_host") / "normals_host")
-    # -ffp-contract=off: no fused multiply-adds, the rounding normals.hip is built with
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", out,
-                           os.path.join(ROOT, "tests", "normals_host", "normals_host.cpp")])
-    return out
+    return host_program.build(tmp_path_factory, "normals_host")
 
 
 def host_normals(exe, *, points=None, depth=None, params=None, models=None, mask=None, edge_rtol=None):
@@ -271,20 +261,10 @@ def host_normals(exe, *, points=None, depth=None, params=None, models=None, mask
         blobs.append(m.tobytes())
     args = [form, Bn, H, W, mb, int(depth is not None), int(edge_rtol is not None), f32_bits(edge_rtol or 0.0)]
     args += list(models) if models is not None else [0] * Bn
-    p = subprocess.run([exe] + [str(a) for a in args], input=b"".join(blobs), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    assert p.returncode == 0, (p.returncode, p.stderr.decode()[-2000:])
-    sizes = [Bn * 3 * n * 4, Bn * n, Bn * 3 * n, Bn * 3 * n * 4 if form else 0]
-    assert len(p.stdout) == sum(sizes), (len(p.stdout), sizes)
-    at = np.cumsum([0] + sizes)
-    part = [p.stdout[at[k]:at[k + 1]] for k in range(4)]
+    part = host_program.run(exe, args, blobs, [Bn * 3 * n * 4, Bn * n, Bn * 3 * n, Bn * 3 * n * 4 if form else 0])
     return dict(normals=np.frombuffer(part[0], F32).reshape(Bn, 3, H, W), valid=np.frombuffer(part[1], np.uint8).reshape(Bn, H, W).astype(bool),
                 rgb=np.frombuffer(part[2], np.uint8).reshape(Bn, 3, H, W),
                 points=np.frombuffer(part[3], F32).reshape(Bn, 3, H, W) if form else None)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def assert_same(got, want, what=""):

@@ -6,13 +6,13 @@ pinned to the live reference where it is present, the C-ABI's descriptors and re
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import camera_project_common as common
+import host_program
 
 ROOT = common.ROOT
 cp, gp = common.cp, common.gp
@@ -111,17 +111,13 @@ def test_reference_rerun_reproduces_golden():
 
 @pytest.fixture(scope="module")
 def proj_host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("proj_host") / "proj_host")
-    # -ffp-contract=off: no fused multiply-adds, the rounding project.hip and splat.hip are built with
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-o", out, os.path.join(ROOT, "tests", "proj_host", "proj_host.cpp")])
+    out = host_program.build(tmp_path_factory, "proj_host", sanitize=False)
 
     def run(model, H, W, row, xyz):
         n = len(xyz)
-        raw = subprocess.run([out, str(model), str(H), str(W), str(n)] + [float(v).hex() for v in row], input=np.ascontiguousarray(xyz, np.float32).tobytes(),
-                             stdout=subprocess.PIPE, check=True).stdout
-        assert len(raw) == n * 13
-        return (np.frombuffer(raw[:8 * n], np.float32).reshape(n, 2), np.frombuffer(raw[8 * n:12 * n], np.float32),
-                np.frombuffer(raw[12 * n:], np.uint8).astype(bool))
+        uv, depth, inside = host_program.run(out, [model, H, W, n] + [float(v).hex() for v in row], [np.ascontiguousarray(xyz, np.float32).tobytes()],
+                                             [8 * n, 4 * n, n])
+        return np.frombuffer(uv, np.float32).reshape(n, 2), np.frombuffer(depth, np.float32), np.frombuffer(inside, np.uint8).astype(bool)
     return run
 
 

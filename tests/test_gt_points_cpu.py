@@ -6,13 +6,13 @@ errors and the C-ABI's descriptor."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import gt_points_common as common
+import host_program
 
 ROOT = common.ROOT
 gp = common.gp
@@ -119,14 +119,12 @@ def test_bars_come_from_the_reference_error():
 
 @pytest.fixture(scope="module")
 def recon_host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("recon_host") / "recon_host")
-    # -ffp-contract=off: no fused multiply-adds, the rounding reconstruct.hip is built with
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-o", out, os.path.join(ROOT, "tests", "recon_host", "recon_host.cpp")])
+    out = host_program.build(tmp_path_factory, "recon_host", sanitize=False)
 
     def run(model, H, W, row):
-        raw = subprocess.check_output([out, str(model), str(H), str(W)] + [float(v).hex() for v in row])
-        steps = int(np.frombuffer(raw[:4], dtype=np.int32)[0])
-        blocks = np.frombuffer(raw[4:], dtype=np.float32).reshape(3, 3, H, W)
+        steps, blocks = host_program.run(out, [model, H, W] + [float(v).hex() for v in row], [], [4, 4 * 9 * H * W])
+        steps = int(np.frombuffer(steps, dtype=np.int32)[0])
+        blocks = np.frombuffer(blocks, dtype=np.float32).reshape(3, 3, H, W)
         return steps, blocks[0], blocks[1], blocks[2]
     return run
 

@@ -6,12 +6,12 @@ of both entry points and the Python argument errors."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_program
 import remap_common as common
 
 ROOT = common.ROOT
@@ -24,18 +24,11 @@ PAD_ID = {"zeros": 0, "border": 1}
 
 @pytest.fixture(scope="module")
 def remap_host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("remap_host") / "remap_host")
-    # -ffp-contract=off: no fused multiply-adds, the rounding remap.hip is built with
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", out,
-                           os.path.join(ROOT, "tests", "remap_host", "remap_host.cpp")])
-    return out
+    return host_program.build(tmp_path_factory, "remap_host")
 
 
 def _run(exe, args, blobs, n_out):
-    p = subprocess.run([exe] + [str(a) for a in args], input=b"".join(blobs), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    assert p.returncode == 0, p.stderr.decode()[-2000:]
-    assert len(p.stdout) == n_out, (len(p.stdout), n_out)
-    return p.stdout
+    return host_program.run(exe, args, blobs, [n_out])[0]
 
 
 def _host_remap(exe, src, uv, cfg, mask, cv, out_u8=False, uv_rows=True, out_rows=True, B=None):

@@ -6,12 +6,12 @@ ud_camera_unproject and the Python argument errors."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_program
 import unproject_common as common
 
 ROOT = common.ROOT
@@ -139,19 +139,13 @@ def test_forms_of_the_restatement_agree_with_their_definitions():
 
 @pytest.fixture(scope="module")
 def unproj_host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("unproj_host") / "unproj_host")
-    # -ffp-contract=off: no fused multiply-adds, the rounding unproject.hip is built with
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", out,
-                           os.path.join(ROOT, "tests", "unproj_host", "unproj_host.cpp")])
+    out = host_program.build(tmp_path_factory, "unproj_host")
 
     def run(model, form, row, uv, depth):
         N = uv.shape[0]
         rec = np.concatenate([uv, depth[:, None]], axis=1).astype(np.float32)
-        raw = subprocess.run([out, str(model), str(form), str(N)] + [float(v).hex() for v in row], input=rec.tobytes(), stdout=subprocess.PIPE,
-                             stderr=subprocess.PIPE, check=True).stdout
-        assert len(raw) == 4 + 12 * N + N
-        return (int(np.frombuffer(raw[:4], dtype=np.int32)[0]), np.frombuffer(raw[4:4 + 12 * N], dtype=np.float32).reshape(N, 3),
-                np.frombuffer(raw[4 + 12 * N:], dtype=np.uint8).astype(bool))
+        k, rays, mask = host_program.run(out, [model, form, N] + [float(v).hex() for v in row], [rec.tobytes()], [4, 12 * N, N])
+        return int(np.frombuffer(k, dtype=np.int32)[0]), np.frombuffer(rays, dtype=np.float32).reshape(N, 3), np.frombuffer(mask, dtype=np.uint8).astype(bool)
     return run
 
 

@@ -2,13 +2,11 @@
 tests/warp_host/warp_host.cpp, and the oracle of the GPU tests -- the composition of the already merged calls (unproject_camera,
 project_camera, remap), never the fused kernel."""
 import functools
-import os
-import struct
-import subprocess
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_program
+from host_program import ROOT, bits, f32_bits as tol_bits  # noqa: F401  (the tests reach them through this module)
+
 PINHOLE, EUCM, SPHERICAL, OPENCV, FISHEYE624, MEI = 1, 2, 3, 4, 5, 6
 NAMES = {PINHOLE: "pinhole", EUCM: "eucm", SPHERICAL: "spherical", OPENCV: "opencv", FISHEYE624: "fisheye624", MEI: "mei"}
 CLOSED = (PINHOLE, EUCM, SPHERICAL, MEI)
@@ -103,10 +101,6 @@ def source_of(c, kind):
     return (c["src_f32"] if dt == np.float32 else c["src_u8"]), (c["src_mask"] if has_mask else None), normalize, odt
 
 
-def tol_bits(tol):
-    return struct.unpack("<i", struct.pack("<f", tol))[0]
-
-
 def host_warp(exe, src, *, depth=None, points=None, params_dst=None, models_dst=None, params_src, models_src, T=None, mode="bilinear",
               padding="zeros", src_mask=None, valid_in=None, normalize=False, out_u8=False, src_depth=None, tol=0.0):
     """tests/warp_host: the fused per-pixel function on numpy inputs, after the program has checked it against the chain of the separate
@@ -131,15 +125,8 @@ def host_warp(exe, src, *, depth=None, points=None, params_dst=None, models_dst=
             int(valid_in is not None), tol_bits(tol)]
     args += list(models_dst) if models_dst is not None else [0] * Bn
     args += list(models_src)
-    p = subprocess.run([exe] + [str(a) for a in args], input=b"".join(blobs), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    assert p.returncode == 0, (p.returncode, p.stderr.decode()[-2000:])
     osz = 1 if out_u8 else 4
-    sizes = [Bn * Cc * n * osz, Bn * n, Bn * n if src_depth is not None else 0, Bn * 2 * n * 4, Bn * n * 4]
-    assert len(p.stdout) == sum(sizes), (len(p.stdout), sizes)
-    parts, at = [], 0
-    for s in sizes:
-        parts.append(p.stdout[at:at + s])
-        at += s
+    parts = host_program.run(exe, args, blobs, [Bn * Cc * n * osz, Bn * n, Bn * n if src_depth is not None else 0, Bn * 2 * n * 4, Bn * n * 4])
     return dict(out=np.frombuffer(parts[0], np.uint8 if out_u8 else np.float32).reshape(Bn, Cc, Ho, Wo),
                 valid=np.frombuffer(parts[1], np.uint8).reshape(Bn, Ho, Wo).astype(bool),
                 visible=np.frombuffer(parts[2], np.uint8).reshape(Bn, Ho, Wo).astype(bool) if src_depth is not None else None,
@@ -147,11 +134,7 @@ def host_warp(exe, src, *, depth=None, points=None, params_dst=None, models_dst=
 
 
 def build_host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("warp_host") / "warp_host")
-    # -ffp-contract=off: no fused multiply-adds, the rounding warp.hip is built with
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", out,
-                           os.path.join(ROOT, "tests", "warp_host", "warp_host.cpp")])
-    return out
+    return host_program.build(tmp_path_factory, "warp_host")
 
 
 def points_in_front(g, n_b, Ho, Wo):
@@ -256,25 +239,5 @@ def oracle(src, *, depth=None, camera=None, points=None, src_camera, transform=N
     return out, valid, visible, uv, dproj
 
 
-def bits(t):
-    """a tensor as integers of its element width: NaN payloads and the sign of a zero count"""
-    import torch
-    t = t.contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.uint8) if t.dtype == torch.bool else t
-
-
 def assert_same(got, want, what=""):
-    """every output, every element, bit for bit; the message says which output and how many elements"""
-    import torch
-    names = ("out", "valid", "visible", "uv", "proj_depth")
-    assert len(got) == len(want) == len(names)
-    for name, a, b in zip(names, got, want):
-        assert (a is None) == (b is None), (what, name)
-        if a is None:
-            continue
-        assert a.dtype == b.dtype and a.shape == b.shape, (what, name, a.dtype, b.dtype, tuple(a.shape), tuple(b.shape))
-        if not torch.equal(bits(a), bits(b)):
-            diff = bits(a) != bits(b)
-            both_nan = (a != a) & (b != b) if a.is_floating_point() else torch.zeros_like(diff)
-            raise AssertionError(f"{what}: {name} differs in {int(diff.sum())} of {diff.numel()} elements "
-                                 f"({int((diff & both_nan).sum())} of them NaN on both sides), first at flat index {int(diff.reshape(-1).nonzero()[0])}")
+    host_program.assert_same(got, want, ("out", "valid", "visible", "uv", "proj_depth"), what)

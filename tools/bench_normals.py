@@ -30,7 +30,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from unidepth_amd import _lib, gtpoints, normals  # noqa: E402
+from unidepth_amd import _args, _lib, gtpoints, normals  # noqa: E402
 from unidepth_amd.ops import check, cur_stream, mk  # noqa: E402
 
 REPS, WINDOWS, TRACE_CALLS = 200, 3, 50
@@ -131,7 +131,7 @@ def alt_depth_call(alt, depth, cam, mask, out):
     """ud_normals of a second build of the library on the same descriptor (the depth form, all outputs)"""
     B, _, H, W = depth.shape
     d = mk(_lib.UdNormals, points=None, depth=depth, params=cam.params, mask=mask.view(torch.uint8), normals=out[0], valid=out[1], rgb=out[2],
-           B=B, H=H, W=W, mask_shared=0, has_rtol=1, rtol_bits=normals._f32_bits(EDGE))
+           B=B, H=H, W=W, mask_shared=0, has_rtol=1, rtol_bits=_args.f32_bits(EDGE))
     for b in range(B):
         d.model[b] = cam.models[b]
 

@@ -18,12 +18,12 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib
-from .cameras import GT_FISHEYE624, GT_OPENCV
+from . import _args, _lib
+from .gtpoints import PreparedCamera, prepare_camera
 from .ops import check, cur_stream, mk
-from .remap import _GPU
-
-_ITERATIVE = (GT_OPENCV, GT_FISHEYE624)
+from .reproject import project_camera
+from .unproject import unproject_camera
+from .warp import warp_camera
 
 
 def invert_rigid(T: torch.Tensor) -> torch.Tensor:
@@ -41,64 +41,35 @@ def invert_rigid(T: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _f32(fn, name, x):
-    """a tolerance as (the value of its fp32 rounding, that rounding's bit pattern)"""
-    try:
-        bits = struct.unpack("<i", struct.pack("<f", float(x)))[0]
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"{fn}: {name} must be a number in fp32's range") from None
-    val = struct.unpack("<f", struct.pack("<i", bits))[0]
-    if not (val >= 0.0 and math.isfinite(val)):
-        raise ValueError(f"{fn}: {name} must be finite and not negative, got {x}")
-    return val, bits
-
-
 def _arguments(fn, depth, camera, src_depths, src_cameras, transforms, px_tol, rel_tol, min_views, valid_in, src_masks):
     """every check both functions share -> the sizes, the tolerances and the tensors in the layout of the descriptor"""
-    from .gtpoints import PreparedCamera, prepare_camera
-    from .unproject import _n_cameras
-    if not isinstance(depth, torch.Tensor) or not depth.is_floating_point():
-        raise ValueError(f"{fn}: depth must be a float tensor, got {getattr(depth, 'dtype', type(depth).__name__)}")
-    if depth.ndim not in (3, 4) or (depth.ndim == 4 and depth.shape[1] != 1) or min(depth.shape) == 0:
-        raise ValueError(f"{fn}: depth must be [B,1,H,W] or [B,H,W], non-empty, got {tuple(depth.shape)}")
-    B, (H, W) = depth.shape[0], depth.shape[-2:]
-    if not isinstance(src_depths, torch.Tensor) or not src_depths.is_floating_point():
-        raise ValueError(f"{fn}: src_depths must be a float tensor, got {getattr(src_depths, 'dtype', type(src_depths).__name__)}")
+    B, H, W = _args.depth_map(fn, "depth", depth)
+    _args.float_tensor(fn, "src_depths", src_depths)
     if src_depths.ndim != 4 or min(src_depths.shape) == 0 or src_depths.shape[0] != B:
         raise ValueError(f"{fn}: src_depths must be [B,V,Hs,Ws] with B = {B}, non-empty, got {tuple(src_depths.shape)}")
     V, Hs, Ws = src_depths.shape[1:]
     if V > 255 or B * V > _lib.UD_RECON_MAX_B:
         raise ValueError(f"{fn}: src_depths: at most 255 views and {_lib.UD_RECON_MAX_B} image-view pairs per call, got B={B} V={V}")
-    if max(H * W, V * Hs * Ws) >= 2 ** 31 - 256:
-        raise ValueError(f"{fn}: unsupported sizes V={V} source={Hs}x{Ws} reference={H}x{W}")
+    _args.max_elems(fn, f"V={V} source={Hs}x{Ws} reference={H}x{W}", H * W, V * Hs * Ws)
     if isinstance(src_cameras, (torch.Tensor, PreparedCamera)) or not isinstance(src_cameras, Sequence) or len(src_cameras) != V:
         raise ValueError(f"{fn}: src_cameras must be a sequence of {V} cameras, one per view")
     for name, cam in [("camera", camera)] + [(f"src_cameras[{v}]", c) for v, c in enumerate(src_cameras)]:
-        k = _n_cameras(cam)
-        if k not in (1, B) or (isinstance(cam, PreparedCamera) and k != B):
-            raise ValueError(f"{fn}: {name} of {k} images for a batch of {B}" + ("" if isinstance(cam, PreparedCamera) else f" (1 or {B} expected)"))
+        _args.batch_of(fn, name, _args.n_cameras(cam), B, shared=not isinstance(cam, PreparedCamera))
     shapes = ((V, 4, 4), (V, 3, 4), (B, V, 4, 4), (B, V, 3, 4))
     if not isinstance(transforms, torch.Tensor) or transforms.dtype != torch.float32 or tuple(transforms.shape) not in shapes:
         raise ValueError(f"{fn}: transforms must be fp32 [{V},4,4], [{B},{V},4,4] or the 3x4 forms of either")
-    px, px_bits = _f32(fn, "px_tol", px_tol)
-    rel, rel_bits = _f32(fn, "rel_tol", rel_tol)
+    px, px_bits = _args.tolerance(fn, "px_tol", px_tol)
+    rel, rel_bits = _args.tolerance(fn, "rel_tol", rel_tol)
     if isinstance(min_views, bool) or not isinstance(min_views, int) or not 0 <= min_views <= V:
         raise ValueError(f"{fn}: min_views must be an integer in 0 .. {V}, got {min_views!r}")
     if valid_in is not None:
-        if not isinstance(valid_in, torch.Tensor) or valid_in.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f"{fn}: valid_in must be a bool or uint8 tensor, got {getattr(valid_in, 'dtype', type(valid_in).__name__)}")
-        if valid_in.ndim not in (3, 4) or tuple(valid_in.shape[-2:]) != (H, W) or valid_in.numel() != B * H * W:
-            raise ValueError(f"{fn}: valid_in {tuple(valid_in.shape)} is not [{B},1,{H},{W}] or [{B},{H},{W}]")
+        _args.image_map(fn, "valid_in", valid_in, H, W, mask=True, B=B, shared=False)
     if src_masks is not None:
-        if not isinstance(src_masks, torch.Tensor) or src_masks.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f"{fn}: src_masks must be a bool or uint8 tensor, got {getattr(src_masks, 'dtype', type(src_masks).__name__)}")
+        _args.mask_tensor(fn, "src_masks", src_masks)
         if tuple(src_masks.shape) != (B, V, Hs, Ws):
             raise ValueError(f"{fn}: src_masks {tuple(src_masks.shape)} is not [{B},{V},{Hs},{Ws}]")
     dev = depth.device
-    others = [t for t in (src_depths, transforms, valid_in, src_masks) if t is not None]
-    others += [c.params for c in (camera, *src_cameras) if isinstance(c, PreparedCamera)]
-    if dev.type != "cuda" or any(t.device != dev for t in others):
-        raise RuntimeError(f"{fn}: {_GPU}")
+    _args.one_gpu(fn, dev, src_depths, transforms, valid_in, src_masks, *_args.prepared_rows(camera, *src_cameras))
     with torch.cuda.device(dev):
         a = dict(B=B, V=V, H=H, W=W, Hs=Hs, Ws=Ws, px=px, px_bits=px_bits, rel=rel, rel_bits=rel_bits, min_views=min_views, dev=dev)
         a["cam"] = prepare_camera(camera, B, dev)
@@ -109,7 +80,7 @@ def _arguments(fn, depth, camera, src_depths, src_cameras, transforms, px_tol, r
         a["Tinv"] = invert_rigid(a["T"])
         a["vin"] = None if valid_in is None else valid_in.reshape(B, H, W).contiguous().view(torch.uint8)
         a["masks"] = None if src_masks is None else src_masks.contiguous().view(torch.uint8)
-    a["iterative"] = any(m in _ITERATIVE for c in (a["cam"], *a["cams"]) for m in c.models)
+    a["iterative"] = _args.n_iterative(a["cam"], *a["cams"]) > 0
     return a
 
 
@@ -123,9 +94,6 @@ def _results(fused, count, mask, cons, epx, erel, return_views, return_errors):
 
 
 def _compose(a, return_views, return_errors):
-    from .reproject import project_camera
-    from .unproject import unproject_camera
-    from .warp import warp_camera
     B, V, H, W, dev = a["B"], a["V"], a["H"], a["W"], a["dev"]
     depth = a["depth"][:, None]                                                     # [B,1,H,W]
     ref_ok = depth > 0
@@ -237,9 +205,8 @@ def depth_consistency(depth: torch.Tensor, camera, src_depths: torch.Tensor, src
                   src_mask=a["masks"], params_src=params_src, T=a["T"], Tinv=a["Tinv"], fused=fused, count=count, mask=mask, consistent=cons,
                   err_px=epx, err_rel=erel, B=B, V=V, H=H, W=W, Hs=a["Hs"], Ws=a["Ws"], nT=a["T"].shape[0], min_views=a["min_views"],
                   px_tol_bits=a["px_bits"], rel_tol_bits=a["rel_bits"])
-        for b in range(B):
-            desc.model_ref[b] = a["cam"].models[b]
-            for v in range(V):
-                desc.model_src[v * B + b] = a["cams"][v].models[b]
+        _args.set_models(desc.model_ref, a["cam"])
+        for v in range(V):
+            _args.set_models(desc.model_src, a["cams"][v], v * B)
         check(_lib.lib.ud_depth_consistency(desc, cur_stream()), "ud_depth_consistency")
     return _results(fused, count, mask.view(torch.bool), None if cons is None else cons.view(torch.bool), epx, erel, return_views, return_errors)

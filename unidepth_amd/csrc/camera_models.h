@@ -184,6 +184,20 @@ UD_CAM_FN void ud_cam_mei_dir(const float* p, float u, float v, float& dx, float
 // UdReconstruct.  Model tags as UdReconstruct.model.
 enum { UD_CAM_PINHOLE = 1, UD_CAM_EUCM = 2, UD_CAM_SPHERICAL = 3, UD_CAM_OPENCV = 4, UD_CAM_FISHEYE624 = 5, UD_CAM_MEI = 6 };
 
+UD_CAM_FN bool ud_cam_model_ok(int m) { return m >= UD_CAM_PINHOLE && m <= UD_CAM_MEI; }
+// closed-form unprojection: every model but OPENCV and Fisheye624, whose radial loop ends on a maximum over the whole image
+UD_CAM_FN bool ud_cam_closed_form(int m) { return m == UD_CAM_PINHOLE || m == UD_CAM_EUCM || m == UD_CAM_SPHERICAL || m == UD_CAM_MEI; }
+
+// The rigid motion t fp32 [3,4] applied to a point in place: x' = ((t0 x + t1 y) + t2 z) + t3, and the same for y' and z' with rows 1
+// and 2.  The association is fixed -- products summed left to right, the translation last, every operation rounded separately: the
+// fused kernels (warp, consistency) have the bits of the separate launches only because all of them move points through this function.
+UD_CAM_FN void ud_cam_move(const float* t, float& x, float& y, float& z) {
+  const float xt = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
+  const float yt = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
+  const float zt = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
+  x = xt; y = yt; z = zt;
+}
+
 // max(x, m) that lets a NaN through, as torch.clamp(min=m) does
 UD_CAM_FN float ud_cam_floor(float x, float m) { return x < m ? m : x; }
 

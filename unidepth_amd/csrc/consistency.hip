@@ -37,18 +37,6 @@ __global__ __launch_bounds__(CS_THREADS) void cs_consistency_kernel(const CsKern
   ud_cs_point(a.p, a.model_ref[b], a.model_src, b, i);
 }
 
-constexpr long long CS_MAX_ELEMS = 0x7fffffffLL - 256;     // element counts of one image stay below 2^31 - 256
-
-bool cs_closed(int m) { return m == UD_CAM_PINHOLE || m == UD_CAM_EUCM || m == UD_CAM_SPHERICAL || m == UD_CAM_MEI; }
-
-// the fp32 behind a bit pattern; finite and >= 0 (false for a NaN)
-bool cs_tolerance(int bits, float* out) {
-  union { int i; float f; } t;
-  t.i = bits;
-  *out = t.f;
-  return t.f >= 0.0f && t.f <= 3.402823466e38f;
-}
-
 }  // namespace
 
 extern "C" int ud_depth_consistency(const UdDepthConsistency* desc, void* stream) {
@@ -62,7 +50,7 @@ extern "C" int ud_depth_consistency(const UdDepthConsistency* desc, void* stream
     return UD_ERR_BAD_ARG;
   }
   const long long n = (long long)d.H * d.W, hw = (long long)d.Hs * d.Ws;
-  if (n >= CS_MAX_ELEMS || hw >= CS_MAX_ELEMS || d.V * hw >= CS_MAX_ELEMS) {
+  if (n >= UD_MAX_ELEMS || hw >= UD_MAX_ELEMS || d.V * hw >= UD_MAX_ELEMS) {
     ud_set_error("ud_depth_consistency: too large (H * W, Hs * Ws and V * Hs * Ws must stay below 2^31 - 256)");
     return UD_ERR_BAD_ARG;
   }
@@ -74,8 +62,8 @@ extern "C" int ud_depth_consistency(const UdDepthConsistency* desc, void* stream
     ud_set_error("ud_depth_consistency: nT must be 1 or B (sets of V matrices)");
     return UD_ERR_BAD_ARG;
   }
-  float px_tol, rel_tol;
-  if (!cs_tolerance(d.px_tol_bits, &px_tol) || !cs_tolerance(d.rel_tol_bits, &rel_tol)) {
+  const float px_tol = ud_f32_from_bits(d.px_tol_bits), rel_tol = ud_f32_from_bits(d.rel_tol_bits);
+  if (!ud_tolerance_ok(px_tol) || !ud_tolerance_ok(rel_tol)) {
     ud_set_error("ud_depth_consistency: px_tol and rel_tol must be finite and not negative");
     return UD_ERR_BAD_ARG;
   }
@@ -85,11 +73,11 @@ extern "C" int ud_depth_consistency(const UdDepthConsistency* desc, void* stream
   }
   for (int k = 0; k < d.B * d.V; ++k) {
     const int ms = d.model_src[k], mr = k < d.B ? d.model_ref[k] : UD_CAM_PINHOLE;
-    if (ms < UD_CAM_PINHOLE || ms > UD_CAM_MEI || mr < UD_CAM_PINHOLE || mr > UD_CAM_MEI) {
+    if (!ud_cam_model_ok(ms) || !ud_cam_model_ok(mr)) {
       ud_set_error("ud_depth_consistency: model tag outside 1..6");
       return UD_ERR_BAD_ARG;
     }
-    if (!cs_closed(ms) || !cs_closed(mr)) {
+    if (!ud_cam_closed_form(ms) || !ud_cam_closed_form(mr)) {
       ud_set_error("ud_depth_consistency: iterative model (OPENCV / Fisheye624), reference or view: its unprojection ends on a maximum over the image; compose the separate calls");
       return UD_ERR_UNSUPPORTED;
     }
@@ -102,10 +90,8 @@ extern "C" int ud_depth_consistency(const UdDepthConsistency* desc, void* stream
   a.p.tol2 = px_tol * px_tol;
   a.p.rel_tol = rel_tol;
   a.p.B = d.B; a.p.V = d.V; a.p.H = d.H; a.p.W = d.W; a.p.Hs = d.Hs; a.p.Ws = d.Ws; a.p.nT = d.nT; a.p.min_views = d.min_views;
-  for (int k = 0; k < UD_RECON_MAX_B; ++k) {
-    a.model_ref[k] = k < d.B ? d.model_ref[k] : 0;
-    a.model_src[k] = k < d.B * d.V ? d.model_src[k] : 0;
-  }
+  ud_copy_models(a.model_ref, d.model_ref, d.B);
+  ud_copy_models(a.model_src, d.model_src, d.B * d.V);
   const dim3 grid((unsigned)((n + CS_THREADS - 1) / CS_THREADS), (unsigned)d.B);
   hipLaunchKernelGGL(cs_consistency_kernel, grid, dim3(CS_THREADS), 0, (hipStream_t)stream, a);
   UD_CHECK_LAUNCH("ud_depth_consistency launch");

@@ -26,14 +26,6 @@ struct UdCsArgs {
   int B, V, H, W, Hs, Ws, nT, min_views;
 };
 
-// x' = ((t0 x + t1 y) + t2 z) + t3, ...: ud_camera_project's association
-UD_RM_FN void ud_cs_move(const float* t, float& x, float& y, float& z) {
-  const float xt = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
-  const float yt = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
-  const float zt = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
-  x = xt; y = yt; z = zt;
-}
-
 // model_ref and every model_src[v * B + b] are closed-form models (Pinhole, EUCM, Spherical, MEI)
 UD_RM_FN void ud_cs_point(const UdCsArgs& a, int model_ref, const unsigned char* model_src, int b, long long i) {
   const size_t n = (size_t)a.n, at = (size_t)b * n + (size_t)i, hw = (size_t)a.Hs * (size_t)a.Ws;
@@ -53,7 +45,7 @@ UD_RM_FN void ud_cs_point(const UdCsArgs& a, int model_ref, const unsigned char*
     const int ms = model_src[v * a.B + b];
     const float* ps = a.params_src + ((size_t)v * (size_t)a.B + (size_t)b) * 16;
     float x = P[0], y = P[1], z = P[2];
-    ud_cs_move(a.T + tv * 12, x, y, z);
+    ud_cam_move(a.T + tv * 12, x, y, z);
     float su, sv;
     ud_cam_project(ms, ps, x, y, z, &su, &sv);
     const float dproj = ud_cam_depth(ms, x, y, z);
@@ -83,7 +75,7 @@ UD_RM_FN void ud_cs_point(const UdCsArgs& a, int model_ref, const unsigned char*
       float Q[3];
       ud_cam_unproject_closed(ms, UD_UNPROJ_DEPTH, ps, su, sv, ds, Q);
       float xb = Q[0], yb = Q[1], zb = Q[2];
-      ud_cs_move(a.Tinv + tv * 12, xb, yb, zb);
+      ud_cam_move(a.Tinv + tv * 12, xb, yb, zb);
       float ru, rv;
       ud_cam_project(model_ref, pr, xb, yb, zb, &ru, &rv);
       const float dback = ud_cam_depth(model_ref, xb, yb, zb);

@@ -104,8 +104,6 @@ __global__ __launch_bounds__(NM_THREADS) void nm_depth_kernel(const NmKernelArgs
 }
 #endif
 
-constexpr long long NM_MAX_ELEMS = 0x7fffffffLL - 256;
-
 // ---- the metrics ------------------------------------------------------------------------------------------------------------------------
 
 constexpr int EN_THREADS = 256, EN_PER_THREAD = 16, EN_CHUNK = EN_THREADS * EN_PER_THREAD;
@@ -328,12 +326,6 @@ __global__ __launch_bounds__(64) void en_select_kernel(const EnArgs a, const int
   for (int t = 0; t < a.T; ++t) out[(size_t)(3 + t) * a.B] = (float)a.cnt[(size_t)b * EN_NCNT + 1 + t] / fn;
 }
 
-float nm_from_bits(int bits) {
-  union { int i; float f; } u;
-  u.i = bits;
-  return u.f;
-}
-
 }  // namespace
 
 extern "C" int ud_normals(const UdNormals* desc, void* stream) {
@@ -342,7 +334,7 @@ extern "C" int ud_normals(const UdNormals* desc, void* stream) {
     return UD_ERR_BAD_ARG;
   }
   const UdNormals& d = *desc;
-  if (d.B < 1 || d.B > UD_RECON_MAX_B || d.H < 1 || d.W < 1 || (long long)d.H * d.W >= NM_MAX_ELEMS) {
+  if (d.B < 1 || d.B > UD_RECON_MAX_B || d.H < 1 || d.W < 1 || (long long)d.H * d.W >= UD_MAX_ELEMS) {
     ud_set_error("ud_normals: bad sizes (1 <= B <= 256, H, W >= 1, H * W < 2^31 - 256)");
     return UD_ERR_BAD_ARG;
   }
@@ -350,8 +342,8 @@ extern "C" int ud_normals(const UdNormals* desc, void* stream) {
     ud_set_error("ud_normals: null pointer (normals; points, or depth with params)");
     return UD_ERR_BAD_ARG;
   }
-  const float rtol = nm_from_bits(d.rtol_bits);
-  if (d.has_rtol && !(rtol >= 0.0f && rtol <= 3.402823466e+38f)) {
+  const float rtol = ud_f32_from_bits(d.rtol_bits);
+  if (d.has_rtol && !ud_tolerance_ok(rtol)) {
     ud_set_error("ud_normals: edge_rtol must be finite and not negative");
     return UD_ERR_BAD_ARG;
   }
@@ -359,17 +351,17 @@ extern "C" int ud_normals(const UdNormals* desc, void* stream) {
   if (!d.points) {
     for (int b = 0; b < d.B; ++b) {
       const int m = d.model[b];
-      if (m < UD_CAM_PINHOLE || m > UD_CAM_MEI) {
+      if (!ud_cam_model_ok(m)) {
         ud_set_error("ud_normals: model tag outside 1..6");
         return UD_ERR_BAD_ARG;
       }
-      if (m == UD_CAM_OPENCV || m == UD_CAM_FISHEYE624) {
+      if (!ud_cam_closed_form(m)) {
         ud_set_error("ud_normals: iterative model (OPENCV / Fisheye624) with depth: unproject with ud_camera_unproject and pass points");
         return UD_ERR_UNSUPPORTED;
       }
     }
   }
-  for (int b = 0; b < UD_RECON_MAX_B; ++b) a.model[b] = (!d.points && b < d.B) ? d.model[b] : 0;
+  ud_copy_models(a.model, d.model, d.points ? 0 : d.B);
   a.p.points = d.points; a.p.depth = d.depth; a.p.mask = d.mask;
   a.p.normals = d.normals; a.p.valid = d.valid; a.p.rgb = d.rgb;
   a.p.mask_bs = d.mask_shared ? 0 : (long long)d.H * d.W;
@@ -422,7 +414,7 @@ extern "C" int ud_eval_normals(const UdEvalNormals* desc, void* workspace, long 
   a.gt = d.gt; a.pred = d.pred; a.mask = d.mask; a.out = d.out; a.count = d.count; a.err = d.error;
   a.cnt = (unsigned*)(w + L.cnt); a.rh = (unsigned*)(w + L.rh); a.sel = (unsigned*)(w + L.sel); a.part = (double*)(w + L.part);
   a.mask_bs = d.mask_shared ? 0 : HW;
-  for (int t = 0; t < EN_MAX_T; ++t) a.cos_t[t] = t < d.T ? nm_from_bits(d.cos_bits[t]) : 2.0f;
+  for (int t = 0; t < EN_MAX_T; ++t) a.cos_t[t] = t < d.T ? ud_f32_from_bits(d.cos_bits[t]) : 2.0f;
   a.B = d.B; a.HW = (int)HW; a.C = (int)((HW + EN_CHUNK - 1) / EN_CHUNK); a.T = d.T;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)a.C, (unsigned)d.B);

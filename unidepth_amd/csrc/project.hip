@@ -34,7 +34,7 @@ __global__ __launch_bounds__(PJ_THREADS) void pj_project_kernel(const PjArgs a) 
   } else {
     x = src[0]; y = src[a.cs]; z = src[2 * a.cs];
   }
-  if (a.T) {
+  if (a.T) {                                               // ud_cam_move (camera_models.h) written out: the call changes this kernel's instruction schedule
     const float* t = a.T + (a.nT == 1 ? 0 : (size_t)b * 12);
     const float xt = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
     const float yt = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
@@ -86,15 +86,13 @@ extern "C" int ud_camera_project(const UdCameraProject* desc, void* stream) {
   a.xyz = d.xyz; a.params = d.params; a.T = d.T; a.uv = d.uv; a.inside = d.inside; a.depth = d.depth;
   a.bs = d.batch_stride; a.ps = d.point_stride; a.cs = d.comp_stride; a.n = d.n_points;
   a.H = d.H; a.W = d.W; a.nT = d.nT; a.uv_rows = d.uv_rows;
-  for (int b = 0; b < UD_RECON_MAX_B; ++b) a.model[b] = 0;
   for (int b = 0; b < d.B; ++b) {
-    const int m = d.model[b];
-    if (m < UD_CAM_PINHOLE || m > UD_CAM_MEI) {
+    if (!ud_cam_model_ok(d.model[b])) {
       ud_set_error("ud_camera_project: model tag outside 1..6");
       return UD_ERR_BAD_ARG;
     }
-    a.model[b] = (unsigned char)m;
   }
+  ud_copy_models(a.model, d.model, d.B);
   if (d.n_points == 0) return UD_OK;
   const dim3 grid((unsigned)((d.n_points + PJ_THREADS - 1) / PJ_THREADS), (unsigned)d.B);
   if (d.comp_stride == 1) hipLaunchKernelGGL(pj_project_kernel<true>, grid, dim3(PJ_THREADS), 0, (hipStream_t)stream, a);

@@ -187,7 +187,7 @@ extern "C" int ud_reconstruct(const UdReconstruct* desc, void* stream) {
   }
   for (int b = 0; b < d.B; ++b) {
     const int m = d.model[b];
-    if (m < RC_PINHOLE || m > RC_MEI) {
+    if (!ud_cam_model_ok(m)) {
       ud_set_error("ud_reconstruct: model tag outside 1..6");
       return UD_ERR_BAD_ARG;
     }

@@ -50,7 +50,6 @@ void rm_launch(const UdRemap& d, hipStream_t s) {
   hipLaunchKernelGGL((rm_remap_kernel<S, O>), grid, dim3(RM_THREADS), 0, s, a);
 }
 
-constexpr long long RM_MAX_ELEMS = 0x7fffffffLL - 256;     // element counts of one image stay below 2^31 - 256
 
 }  // namespace
 
@@ -64,8 +63,8 @@ extern "C" int ud_remap(const UdRemap* desc, void* stream) {
     ud_set_error("ud_remap: bad sizes (1 <= B <= 256, C, Hs, Ws, n_points >= 1)");
     return UD_ERR_BAD_ARG;
   }
-  if (d.n_points >= RM_MAX_ELEMS || (long long)d.Hs * d.Ws >= RM_MAX_ELEMS || d.C * ((long long)d.Hs * d.Ws) >= RM_MAX_ELEMS ||
-      d.C * d.n_points >= RM_MAX_ELEMS) {
+  if (d.n_points >= UD_MAX_ELEMS || (long long)d.Hs * d.Ws >= UD_MAX_ELEMS || d.C * ((long long)d.Hs * d.Ws) >= UD_MAX_ELEMS ||
+      d.C * d.n_points >= UD_MAX_ELEMS) {
     ud_set_error("ud_remap: too large (n_points, C * n_points and C * Hs * Ws must stay below 2^31 - 256)");
     return UD_ERR_BAD_ARG;
   }
@@ -107,7 +106,7 @@ extern "C" int ud_overlap_mask(const UdOverlapMask* desc, void* stream) {
     ud_set_error("ud_overlap_mask: bad sizes (1 <= B <= 256, H, W >= 2: the sample grid divides by H - 1 and W - 1)");
     return UD_ERR_BAD_ARG;
   }
-  if ((long long)d.H * d.W >= RM_MAX_ELEMS) {
+  if ((long long)d.H * d.W >= UD_MAX_ELEMS) {
     ud_set_error("ud_overlap_mask: too large (H * W must stay below 2^31 - 256)");
     return UD_ERR_BAD_ARG;
   }

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_splat_kernel(SpArgs a, const PR
     } else {
       x = src[0]; y = src[a.cs]; z = src[2 * a.cs];
     }
-    if (a.T) {
+    if (a.T) {                                             // ud_cam_move (camera_models.h) written out: the call changes this kernel's instruction schedule
       const float* t = a.T + (a.nT == 1 ? 0 : (size_t)b * 12);
       const float xt = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
       const float yt = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
@@ -345,15 +345,13 @@ extern "C" int ud_splat_camera(const UdSplatCamera* desc, void* stream) {
   }
   SpProjCamera proj;
   proj.params = d.params; proj.cos_limit = d.cos_limit;
-  for (int b = 0; b < UD_RECON_MAX_B; ++b) proj.model[b] = 0;
   for (int b = 0; b < d.B; ++b) {
-    const int m = d.model[b];
-    if (m < UD_CAM_PINHOLE || m > UD_CAM_MEI) {
+    if (!ud_cam_model_ok(d.model[b])) {
       ud_set_error("ud_splat_camera: model tag outside 1..6");
       return UD_ERR_BAD_ARG;
     }
-    proj.model[b] = (unsigned char)m;
   }
+  ud_copy_models(proj.model, d.model, d.B);
   rc = sp_check_rest_and_fill(d, "ud_splat_camera", a);
   if (rc != UD_OK) return rc;
   return sp_launch(a, proj, stream, "ud_splat_camera launch");

@@ -79,6 +79,20 @@ __device__ __forceinline__ float ud_wave_sum(float v) {
 }
 
 void ud_set_error(const char* msg);
+
+// ---- host side of the camera-map entry points (reconstruct, project, unproject, splat, remap, warp, normals, consistency): the small
+// checks each of them makes before its launch
+constexpr long long UD_MAX_ELEMS = 0x7fffffffLL - 256;     // element counts of one image stay below 2^31 - 256
+static inline float ud_f32_from_bits(int bits) {           // the fp32 a descriptor carries as its bit pattern
+  union { int i; float f; } u;
+  u.i = bits;
+  return u.f;
+}
+static inline bool ud_tolerance_ok(float t) { return t >= 0.0f && t <= 3.402823466e38f; }      // finite and >= 0 (false for a NaN)
+// the first n model tags of a descriptor into the fixed array of a kernel's arguments, zeros behind them
+static inline void ud_copy_models(unsigned char (&dst)[UD_RECON_MAX_B], const unsigned char* src, int n) {
+  for (int k = 0; k < UD_RECON_MAX_B; ++k) dst[k] = k < n ? src[k] : 0;
+}
 #define UD_MAX_DEVICES 64
 bool ud_attr_once(bool (&done)[UD_MAX_DEVICES]);   // true if the calling kernel's launch attribute was already set on the current device
 #ifdef UD_TOOLS

@@ -137,7 +137,7 @@ extern "C" int ud_camera_unproject(const UdCameraUnproject* desc, void* stream) 
     return UD_ERR_BAD_ARG;
   }
   const UdCameraUnproject& d = *desc;
-  if (d.B < 1 || d.B > UD_RECON_MAX_B || d.H < 1 || d.W < 1 || d.n_points < 0 || d.n_points > 0x7fffffffLL - 256) {
+  if (d.B < 1 || d.B > UD_RECON_MAX_B || d.H < 1 || d.W < 1 || d.n_points < 0 || d.n_points > UD_MAX_ELEMS) {
     ud_set_error("ud_camera_unproject: bad sizes (1 <= B <= 256, H, W >= 1, 0 <= n_points < 2^31 - 256)");
     return UD_ERR_BAD_ARG;
   }
@@ -167,7 +167,7 @@ extern "C" int ud_camera_unproject(const UdCameraUnproject* desc, void* stream) 
   }
   for (int b = 0; b < d.B; ++b) {
     const int m = d.model[b];
-    if (m < UD_CAM_PINHOLE || m > UD_CAM_MEI) {
+    if (!ud_cam_model_ok(m)) {
       ud_set_error("ud_camera_unproject: model tag outside 1..6");
       return UD_ERR_BAD_ARG;
     }

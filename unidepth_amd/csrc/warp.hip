@@ -47,20 +47,14 @@ void wp_launch(const UdWarpCamera& d, hipStream_t s) {
   a.p.src_bs = d.src_shared ? 0 : d.C * hw;
   a.p.mask_bs = d.mask_shared ? 0 : hw;
   a.p.sdepth_bs = d.depth_shared ? 0 : hw;
-  union { int i; float f; } tol;
-  tol.i = d.tol_bits;
-  a.p.tol = tol.f;
+  a.p.tol = ud_f32_from_bits(d.tol_bits);
   a.p.C = d.C; a.p.Wo = d.Wo; a.p.Hs = d.Hs; a.p.Ws = d.Ws; a.p.nT = d.nT; a.p.mode = d.mode; a.p.padding = d.padding;
   a.p.normalize = d.normalize ? 1 : 0;
-  for (int b = 0; b < UD_RECON_MAX_B; ++b) {
-    a.model_dst[b] = b < d.B ? d.model_dst[b] : 0;
-    a.model_src[b] = b < d.B ? d.model_src[b] : 0;
-  }
+  ud_copy_models(a.model_dst, d.model_dst, d.B);
+  ud_copy_models(a.model_src, d.model_src, d.B);
   const dim3 grid((unsigned)((n + WP_THREADS - 1) / WP_THREADS), (unsigned)d.B);
   hipLaunchKernelGGL((wp_warp_kernel<S, O>), grid, dim3(WP_THREADS), 0, s, a);
 }
-
-constexpr long long WP_MAX_ELEMS = 0x7fffffffLL - 256;     // element counts of one image stay below 2^31 - 256
 
 }  // namespace
 
@@ -75,7 +69,7 @@ extern "C" int ud_warp_camera(const UdWarpCamera* desc, void* stream) {
     return UD_ERR_BAD_ARG;
   }
   const long long n = (long long)d.Ho * d.Wo, hw = (long long)d.Hs * d.Ws;
-  if (n >= WP_MAX_ELEMS || hw >= WP_MAX_ELEMS || d.C * hw >= WP_MAX_ELEMS || d.C * n >= WP_MAX_ELEMS) {
+  if (n >= UD_MAX_ELEMS || hw >= UD_MAX_ELEMS || d.C * hw >= UD_MAX_ELEMS || d.C * n >= UD_MAX_ELEMS) {
     ud_set_error("ud_warp_camera: too large (Ho * Wo, C * Ho * Wo and C * Hs * Ws must stay below 2^31 - 256)");
     return UD_ERR_BAD_ARG;
   }
@@ -105,11 +99,11 @@ extern "C" int ud_warp_camera(const UdWarpCamera* desc, void* stream) {
   }
   for (int b = 0; b < d.B; ++b) {
     const int ms = d.model_src[b], md = d.model_dst[b];
-    if (ms < UD_CAM_PINHOLE || ms > UD_CAM_MEI || (d.depth && (md < UD_CAM_PINHOLE || md > UD_CAM_MEI))) {
+    if (!ud_cam_model_ok(ms) || (d.depth && !ud_cam_model_ok(md))) {
       ud_set_error("ud_warp_camera: model tag outside 1..6");
       return UD_ERR_BAD_ARG;
     }
-    if (d.depth && (md == UD_CAM_OPENCV || md == UD_CAM_FISHEYE624)) {
+    if (d.depth && !ud_cam_closed_form(md)) {
       ud_set_error("ud_warp_camera: iterative destination (OPENCV / Fisheye624) with depth: unproject with ud_camera_unproject and pass points");
       return UD_ERR_UNSUPPORTED;
     }

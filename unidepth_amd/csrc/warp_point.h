@@ -44,13 +44,7 @@ UD_RM_FN void ud_wp_point(const UdWpArgs<S, O>& a, int model_dst, int model_src,
     cv = cv && d > 0.0f;                               // false for a NaN; the model's unprojection mask is deliberately not part of it
   }
   // b. the rigid motion, ud_camera_project's arithmetic
-  if (a.T) {
-    const float* t = a.T + (a.nT == 1 ? 0 : (size_t)b * 12);
-    const float xt = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
-    const float yt = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
-    const float zt = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
-    x = xt; y = yt; z = zt;
-  }
+  if (a.T) ud_cam_move(a.T + (a.nT == 1 ? 0 : (size_t)b * 12), x, y, z);
   // c. the projection through the source camera
   float u, v;
   ud_cam_project(model_src, a.params_src + (size_t)b * 16, x, y, z, &u, &v);

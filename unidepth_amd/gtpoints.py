@@ -15,20 +15,10 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
-from .cameras import BatchCamera, GT_FISHEYE624, GT_OPENCV, GT_PINHOLE, as_camera
+from . import _args, _lib
+from ._args import PreparedCamera
+from .cameras import BatchCamera, GT_PINHOLE, as_camera
 from .ops import check, cur_stream, mk
-
-
-class PreparedCamera:
-    """Parameter rows fp32 [B,16] on the device and the model tag of every image: what ud_reconstruct takes.  Made by
-    prepare_camera(); gt_points accepts it in place of a camera and then copies nothing from the host."""
-
-    def __init__(self, params: torch.Tensor, models):
-        self.params, self.models = params, tuple(int(m) for m in models)
-
-    def __len__(self):
-        return len(self.models)
 
 
 def _pinhole_rows(K: torch.Tensor, B: int) -> torch.Tensor:
@@ -36,8 +26,7 @@ def _pinhole_rows(K: torch.Tensor, B: int) -> torch.Tensor:
         K = K[None]
     if K.ndim != 3 or tuple(K.shape[-2:]) != (3, 3) or not K.is_floating_point():
         raise ValueError(f"gt_points: an intrinsics tensor must be a float [3,3] or [B,3,3], got {tuple(K.shape)} {K.dtype}")
-    if K.shape[0] not in (1, B):
-        raise ValueError(f"gt_points: {K.shape[0]} intrinsics for a batch of {B} (1 or {B} expected)")
+    _args.batch_of("gt_points", "camera", K.shape[0], B)
     K = K.to(torch.float32)
     rows = torch.zeros(K.shape[0], 16, dtype=torch.float32, device=K.device)
     rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3] = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
@@ -56,8 +45,7 @@ def prepare_camera(camera, B: int, device) -> PreparedCamera:
     a Pinhole / EUCM / Spherical with 1 or B rows, one OPENCV / Fisheye624 / MEI (applied to every image), a BatchCamera of B
     members of any mix of models, or objects of the reference's classes (cameras.as_camera).  The camera is not modified."""
     if isinstance(camera, PreparedCamera):
-        if len(camera) != B:
-            raise ValueError(f"gt_points: a prepared camera of {len(camera)} images for a batch of {B}")
+        _args.batch_of("gt_points", "camera", len(camera), B, shared=False)
         return camera
     if isinstance(camera, torch.Tensor):
         rows, models = _pinhole_rows(camera, B), (GT_PINHOLE,)
@@ -65,19 +53,15 @@ def prepare_camera(camera, B: int, device) -> PreparedCamera:
         cam = as_camera(camera)
         if isinstance(cam, BatchCamera):
             rows, models = cam.params, cam.gt_modes
-            if len(models) != B:
-                raise ValueError(f"gt_points: a BatchCamera of {len(models)} cameras for a batch of {B}")
+            _args.batch_of("gt_points", "camera", len(models), B, shared=False)
         else:
             n, k = cam.params.shape
-            if n not in (1, B):
-                raise ValueError(f"gt_points: {type(cam).__name__} with {n} cameras for a batch of {B} (1 or {B} expected)")
+            _args.batch_of("gt_points", "camera", n, B)
             rows = torch.zeros(n, 16, dtype=torch.float32, device=cam.params.device)
             rows[:, :k] = cam.params
             models = (cam.gt_mode,)
-    if B > _lib.UD_RECON_MAX_B:
-        raise ValueError(f"gt_points: at most {_lib.UD_RECON_MAX_B} images per call, got {B}")
-    if torch.device(device).type != "cuda":
-        raise RuntimeError("gt_points: GPU tensors expected (the HIP kernels are the only implementation)")
+    _args.max_images("gt_points", B)
+    _args.one_gpu("gt_points", torch.device(device))
     rows = rows.to(device=device, dtype=torch.float32)
     if rows.shape[0] != B:
         rows = rows.expand(B, 16)
@@ -97,31 +81,19 @@ def gt_points(depth: torch.Tensor, camera) -> torch.Tensor:
     Stream-ordered, nothing synchronises.  Camera objects and host tensors are uploaded with one small copy, which a graph capture
     does not allow: capture with a prepare_camera() result or with an intrinsics tensor that is already on the device.  A skewed
     intrinsics tensor raises ValueError when it is on the host; on the device its images come back NaN (no read-back)."""
-    if not isinstance(depth, torch.Tensor) or not depth.is_floating_point():
-        raise ValueError(f"gt_points: depth must be a float tensor, got {getattr(depth, 'dtype', type(depth).__name__)}")
-    if depth.ndim == 4 and depth.shape[1] == 1:
-        B, _, H, W = depth.shape
-    elif depth.ndim == 3:
-        B, H, W = depth.shape
-    else:
-        raise ValueError(f"gt_points: depth must be [B,1,H,W] or [B,H,W], got {tuple(depth.shape)}")
-    if B == 0 or H * W == 0:
-        raise ValueError("gt_points: empty batch or empty maps")
-    if B > _lib.UD_RECON_MAX_B:
-        raise ValueError(f"gt_points: at most {_lib.UD_RECON_MAX_B} images per call, got {B}")
+    B, H, W = _args.depth_map("gt_points", "depth", depth)
+    _args.max_images("gt_points", B)
     if _lib.lib.ud_reconstruct_work_bytes(B, H, W, 0) < 0:
         raise ValueError(f"gt_points: unsupported sizes B={B} H={H} W={W}")
     cam = prepare_camera(camera, B, depth.device)
-    if not depth.is_cuda or cam.params.device != depth.device:
-        raise RuntimeError("gt_points: GPU tensors on one device expected (the HIP kernels are the only implementation)")
+    _args.one_gpu("gt_points", depth.device, cam.params)
     d = depth.reshape(B, 1, H, W).float().contiguous()
     points = torch.empty(B, 3, H, W, device=d.device, dtype=torch.float32)
-    n_iter = sum(m in (GT_OPENCV, GT_FISHEYE624) for m in cam.models)
+    n_iter = _args.n_iterative(cam)
     nbytes = int(_lib.lib.ud_reconstruct_work_bytes(B, H, W, n_iter))
     work = torch.empty(nbytes, device=d.device, dtype=torch.uint8) if nbytes else None
     desc = mk(_lib.UdReconstruct, depth=d, params=cam.params, points=points, work=work, work_bytes=nbytes, B=B, H=H, W=W)
-    for b, m in enumerate(cam.models):
-        desc.model[b] = m
+    _args.set_models(desc.model, cam)
     with torch.cuda.device(d.device):
         check(_lib.lib.ud_reconstruct(desc, cur_stream()), "ud_reconstruct")
     return points

@@ -10,52 +10,25 @@ The HIP kernels are the only implementation: CPU tensors raise."""
 from __future__ import annotations
 
 import math
-import struct
 from typing import Optional, Sequence
 
 import torch
 
-from . import _lib
-from .cameras import GT_FISHEYE624, GT_OPENCV
+from . import _args, _lib
+from .gtpoints import prepare_camera
 from .ops import check, cur_stream, mk
-
-_GPU = "GPU tensors on one device expected (the HIP kernels are the only implementation)"
-_ITERATIVE = (GT_OPENCV, GT_FISHEYE624)
-
-
-def _f32_bits(v: float) -> int:
-    return struct.unpack("<i", struct.pack("<f", v))[0]
+from .unproject import unproject_camera
 
 
 def _rtol(fn, edge_rtol):
     """(has_rtol, rtol_bits): the descriptor carries the fp32's bit pattern"""
-    if edge_rtol is None:
-        return 0, 0
-    try:
-        r = float(edge_rtol)
-        bits = _f32_bits(r)
-    except (TypeError, ValueError, OverflowError, struct.error):
-        raise ValueError(f"{fn}: edge_rtol must be a number in fp32's range") from None
-    if not (r >= 0.0 and math.isfinite(r)):
-        raise ValueError(f"{fn}: edge_rtol must be finite and not negative, got {r}")
-    return 1, bits
-
-
-def _map(fn, name, t, B, H, W, float_ok, shared_ok):
-    """a [B,1,H,W] / [B,H,W] map (a batch of 1 is shared where shared_ok): a mask (bool / uint8) or a depth (any float dtype) -> its batch"""
-    kind = "a float" if float_ok else "a bool or uint8"
-    good = isinstance(t, torch.Tensor) and (t.is_floating_point() if float_ok else t.dtype in (torch.bool, torch.uint8))
-    if not good:
-        raise ValueError(f"{fn}: {name} must be {kind} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if t.ndim not in (3, 4) or (t.ndim == 4 and t.shape[1] != 1) or tuple(t.shape[-2:]) != (H, W) or t.shape[0] not in ((1, B) if shared_ok else (B,)):
-        raise ValueError(f"{fn}: {name} {tuple(t.shape)} is not [B,1,{H},{W}] or [B,{H},{W}] with B = {B}{' or 1' if shared_ok else ''}")
-    return t.shape[0]
+    return (0, 0) if edge_rtol is None else (1, _args.tolerance(fn, "edge_rtol", edge_rtol)[1])
 
 
 def _sizes(fn, B, H, W):
-    if B > _lib.UD_RECON_MAX_B:
-        raise ValueError(f"{fn}: at most {_lib.UD_RECON_MAX_B} images per call, got {B}")
-    if H * W >= 2 ** 31 - 4096 or H > 524280:
+    _args.max_images(fn, B)
+    _args.max_elems(fn, f"H={H} W={W}", H * W)
+    if H > 524280:                                                    # the launch grid's rows of tiles
         raise ValueError(f"{fn}: unsupported sizes H={H} W={W}")
 
 
@@ -70,15 +43,14 @@ def _run(fn, *, points, depth, cam, mask, edge_rtol, return_mask, return_rgb, B,
                   valid=valid, rgb=rgb, B=B, H=H, W=W, mask_shared=int(m is not None and m.shape[0] == 1 and B > 1), has_rtol=has_rtol,
                   rtol_bits=rtol_bits)
         if cam is not None:
-            for b in range(B):
-                desc.model[b] = cam.models[b]
+            _args.set_models(desc.model, cam)
         check(_lib.lib.ud_normals(desc, cur_stream()), "ud_normals")
     res = (normals,)
     if return_mask:
         res += (valid.view(torch.bool),)
     if return_rgb:
         res += (rgb,)
-    return res if len(res) > 1 else res[0]
+    return _args.tail(res)
 
 
 def normals_from_points(points: torch.Tensor, *, mask: Optional[torch.Tensor] = None, depth: Optional[torch.Tensor] = None,
@@ -105,20 +77,15 @@ def normals_from_points(points: torch.Tensor, *, mask: Optional[torch.Tensor] = 
 
     One launch, stream-ordered, nothing synchronises, no workspace: captures into a graph."""
     fn = "normals_from_points"
-    if not isinstance(points, torch.Tensor) or not points.is_floating_point():
-        raise ValueError(f"{fn}: points must be a float tensor, got {getattr(points, 'dtype', type(points).__name__)}")
-    if points.ndim != 4 or points.shape[1] != 3 or min(points.shape) == 0:
-        raise ValueError(f"{fn}: points must be [B,3,H,W], non-empty, got {tuple(points.shape)}")
-    B, _, H, W = points.shape
+    B, H, W = _args.point_map(fn, "points", points)
     _sizes(fn, B, H, W)
     if mask is not None:
-        _map(fn, "mask", mask, B, H, W, False, True)
+        _args.image_map(fn, "mask", mask, H, W, mask=True, B=B)
     if depth is not None:
-        _map(fn, "depth", depth, B, H, W, True, False)
+        _args.image_map(fn, "depth", depth, H, W, mask=False, B=B, shared=False)
     _rtol(fn, edge_rtol)
     dev = points.device
-    if dev.type != "cuda" or any(t.device != dev for t in (mask, depth) if t is not None):
-        raise RuntimeError(f"{fn}: {_GPU}")
+    _args.one_gpu(fn, dev, mask, depth)
     with torch.cuda.device(dev):
         p = points.float().contiguous()
         d = None if depth is None else depth.reshape(B, H, W).float().contiguous()
@@ -145,26 +112,18 @@ def normals_camera(depth: torch.Tensor, camera, *, mask: Optional[torch.Tensor] 
     One launch.  With an OPENCV or Fisheye624 member in the camera, whose radial loop ends on a maximum over the whole image, the points
     of the whole batch come from unproject_camera first and `depth > 0` is ANDed into the mask: five launches (three of
     unproject_camera, one comparison, the normals), six with a mask.  Stream-ordered, nothing synchronises: captures into a graph."""
-    from .gtpoints import PreparedCamera, prepare_camera
-    from .unproject import unproject_camera
     fn = "normals_camera"
-    if not isinstance(depth, torch.Tensor) or not depth.is_floating_point():
-        raise ValueError(f"{fn}: depth must be a float tensor, got {getattr(depth, 'dtype', type(depth).__name__)}")
-    if depth.ndim not in (3, 4) or (depth.ndim == 4 and depth.shape[1] != 1) or min(depth.shape) == 0:
-        raise ValueError(f"{fn}: depth must be [B,1,H,W] or [B,H,W], non-empty, got {tuple(depth.shape)}")
-    B, (H, W) = depth.shape[0], depth.shape[-2:]
+    B, H, W = _args.depth_map(fn, "depth", depth)
     _sizes(fn, B, H, W)
     if mask is not None:
-        _map(fn, "mask", mask, B, H, W, False, True)
+        _args.image_map(fn, "mask", mask, H, W, mask=True, B=B)
     _rtol(fn, edge_rtol)
     dev = depth.device
-    others = [t for t in (mask,) if t is not None] + ([camera.params] if isinstance(camera, PreparedCamera) else [])
-    if dev.type != "cuda" or any(t.device != dev for t in others):
-        raise RuntimeError(f"{fn}: {_GPU}")
+    _args.one_gpu(fn, dev, mask, *_args.prepared_rows(camera))
     with torch.cuda.device(dev):
         cam = prepare_camera(camera, B, dev)
         d = depth.reshape(B, H, W).float().contiguous()
-        if any(m in _ITERATIVE for m in cam.models):              # not fused: the radial loop ends on a maximum over the image
+        if _args.n_iterative(cam):                                # not fused: the radial loop ends on a maximum over the image
             points = unproject_camera(None, cam, depth=d, image_shape=(H, W))
             positive = (d > 0).view(B, 1, H, W)
             mask = positive if mask is None else positive & mask.reshape(-1, 1, H, W).bool()
@@ -194,16 +153,13 @@ def eval_normals(gt: torch.Tensor, pred: torch.Tensor, mask: Optional[torch.Tens
     comes from torch's allocator.  Stream-ordered: captures into a graph."""
     fn = "eval_normals"
     for name, t in (("gt", gt), ("pred", pred)):
-        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
-            raise ValueError(f"{fn}: {name} must be a float tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-        if t.ndim != 4 or t.shape[1] != 3 or min(t.shape) == 0:
-            raise ValueError(f"{fn}: {name} must be [B,3,H,W], non-empty, got {tuple(t.shape)}")
+        _args.point_map(fn, name, t)
     if gt.shape != pred.shape:
         raise ValueError(f"{fn}: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} differ in shape")
     B, _, H, W = gt.shape
     _sizes(fn, B, H, W)
     if mask is not None:
-        _map(fn, "mask", mask, B, H, W, False, True)
+        _args.image_map(fn, "mask", mask, H, W, mask=True, B=B)
     try:
         thr = [float(t) for t in thresholds]
     except (TypeError, ValueError):
@@ -213,8 +169,7 @@ def eval_normals(gt: torch.Tensor, pred: torch.Tensor, mask: Optional[torch.Tens
     if not all(math.isfinite(t) and 0.0 < t <= 180.0 for t in thr):
         raise ValueError(f"{fn}: thresholds must be angles in (0, 180] degrees, got {thr}")
     dev = gt.device
-    if dev.type != "cuda" or any(t.device != dev for t in (pred, mask) if t is not None):
-        raise RuntimeError(f"{fn}: {_GPU}")
+    _args.one_gpu(fn, dev, pred, mask)
     T = len(thr)
     with torch.cuda.device(dev):
         g, p = gt.float().contiguous(), pred.float().contiguous()
@@ -229,7 +184,7 @@ def eval_normals(gt: torch.Tensor, pred: torch.Tensor, mask: Optional[torch.Tens
         desc = mk(_lib.UdEvalNormals, gt=g, pred=p, mask=m, out=out, count=count, error=err, B=B, H=H, W=W, T=T,
                   mask_shared=int(m is not None and m.shape[0] == 1 and B > 1))
         for k, t in enumerate(thr):
-            desc.cos_bits[k] = _f32_bits(math.cos(math.radians(t)))
+            desc.cos_bits[k] = _args.f32_bits(math.cos(math.radians(t)))
         check(_lib.lib.ud_eval_normals(desc, work.data_ptr(), nbytes, cur_stream()), "ud_eval_normals")
     res = {"mean": out[0], "median": out[1], "rmse": out[2]}
     for k, t in enumerate(thresholds):

@@ -18,21 +18,15 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _args, _lib
+from .cameras import GT_PINHOLE
+from .gtpoints import PreparedCamera, prepare_camera
 from .ops import check, cur_stream, mk
+from .reproject import project_camera
+from .unproject import unproject_camera
 
-_GPU = "GPU tensors on one device expected (the HIP kernels are the only implementation)"
 _MODES = {"nearest": _lib.UD_REMAP_NEAREST, "bilinear": _lib.UD_REMAP_BILINEAR}
 _PADDINGS = {"zeros": _lib.UD_REMAP_ZEROS, "border": _lib.UD_REMAP_BORDER}
-
-
-def _per_point(fn, name, t, n, tail, rows):
-    """a uint8 / bool tensor with one value per point: [b,1,H,W] / [b,H,W] for a planar uv, [b,N] for rows -> its batch"""
-    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"{fn}: {name} must be a bool or uint8 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if t.ndim < 2 or t.shape[0] == 0 or t.numel() != t.shape[0] * n or (rows and t.ndim != 2) or (not rows and tuple(t.shape[-2:]) != tail):
-        raise ValueError(f"{fn}: {name} {tuple(t.shape)} does not hold one value for each of the {tail} coordinates of every image")
-    return t.shape[0]
 
 
 def remap(src: torch.Tensor, uv: torch.Tensor, *, mode: str = "bilinear", padding: str = "zeros", src_mask: Optional[torch.Tensor] = None,
@@ -77,41 +71,21 @@ def remap(src: torch.Tensor, uv: torch.Tensor, *, mode: str = "bilinear", paddin
         raise ValueError(f"{fn}: out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
     if out_dtype == torch.uint8 and not src_u8:
         raise ValueError(f"{fn}: a uint8 output needs a uint8 source, got {src.dtype}")
-    if not isinstance(uv, torch.Tensor) or not uv.is_floating_point():
-        raise ValueError(f"{fn}: uv must be a float tensor, got {getattr(uv, 'dtype', type(uv).__name__)}")
-    if uv.ndim == 4 and uv.shape[1] == 2:
-        nb, tail, rows = uv.shape[0], tuple(uv.shape[2:]), 0
-        n = tail[0] * tail[1]
-        strides = (2 * n, 1, n)
-    elif uv.ndim == 3 and uv.shape[2] == 2:
-        nb, tail, rows = uv.shape[0], (uv.shape[1],), 1
-        n = tail[0]
-        strides = (2 * n, 2, 1)
-    else:
-        raise ValueError(f"{fn}: uv must be [B,2,H,W] or [B,N,2] (B or 1 images), got {tuple(uv.shape)}")
+    _args.float_tensor(fn, "uv", uv)
+    nb, n, tail, rows, strides = _args.layout(fn, "uv", uv, 2)
     if nb == 0 or n == 0:
         raise ValueError(f"{fn}: empty uv {tuple(uv.shape)}")
     sizes = {"src": sb, "uv": nb}
     if src_mask is not None:
-        if not isinstance(src_mask, torch.Tensor) or src_mask.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f"{fn}: src_mask must be a bool or uint8 tensor, got {getattr(src_mask, 'dtype', type(src_mask).__name__)}")
-        if src_mask.ndim not in (3, 4) or src_mask.shape[0] == 0 or tuple(src_mask.shape[-2:]) != (Hs, Ws) or src_mask.numel() != src_mask.shape[0] * Hs * Ws:
-            raise ValueError(f"{fn}: src_mask {tuple(src_mask.shape)} is not [B,1,{Hs},{Ws}] (B or 1 images)")
-        sizes["src_mask"] = src_mask.shape[0]
+        sizes["src_mask"] = _args.image_map(fn, "src_mask", src_mask, Hs, Ws, mask=True)
     if coord_valid is not None:
-        sizes["coord_valid"] = _per_point(fn, "coord_valid", coord_valid, n, tail, rows)
+        sizes["coord_valid"] = _args.per_point(fn, "coord_valid", coord_valid, n, tail, rows)
     B = max(sizes.values())
-    for name, k in sizes.items():
-        if k not in (1, B):
-            raise ValueError(f"{fn}: {name} of {k} images for a batch of {B} (1 or {B} expected)")
-    if B > _lib.UD_RECON_MAX_B:
-        raise ValueError(f"{fn}: at most {_lib.UD_RECON_MAX_B} images per call, got {B}")
-    if max(n, Cc * n, Cc * Hs * Ws) >= 2 ** 31 - 256:
-        raise ValueError(f"{fn}: unsupported sizes C={Cc} source={Hs}x{Ws} points={n}")
+    _args.batches(fn, sizes, B)
+    _args.max_images(fn, B)
+    _args.max_elems(fn, f"C={Cc} source={Hs}x{Ws} points={n}", n, Cc * n, Cc * Hs * Ws)
     dev = src.device
-    others = [t for t in (uv, src_mask, coord_valid) if t is not None]
-    if dev.type != "cuda" or any(t.device != dev for t in others):
-        raise RuntimeError(f"{fn}: {_GPU}")
+    _args.one_gpu(fn, dev, uv, src_mask, coord_valid)
     with torch.cuda.device(dev):
         s = src.contiguous() if src_u8 else src.float().contiguous()
         coords = uv.float().contiguous()
@@ -152,27 +126,16 @@ def undistort(src: torch.Tensor, src_camera, dst_camera=None, out_shape: Optiona
 
     Values are RESAMPLED, not converted: a depth map moved between a model whose depth is z and Spherical, whose depth is the distance
     along the ray, keeps its numbers.  Converting them is the caller's business."""
-    from .gtpoints import PreparedCamera, prepare_camera
-    from .cameras import GT_PINHOLE
-    from .reproject import project_camera
-    from .unproject import _n_cameras, unproject_camera
     fn = "undistort"
     if not isinstance(src, torch.Tensor) or src.ndim != 4 or min(src.shape) == 0:
         raise ValueError(f"{fn}: src must be [B,C,Hs,Ws], non-empty, got {tuple(getattr(src, 'shape', ()))}")
     Hs, Ws = src.shape[-2:]
     if out_shape is None:
         out_shape = (Hs, Ws)
-    try:
-        Ho, Wo = (int(v) for v in out_shape)
-    except (TypeError, ValueError):
-        raise ValueError(f"{fn}: out_shape must be (H, W)") from None
-    if Ho <= 0 or Wo <= 0:
-        raise ValueError(f"{fn}: out_shape must be positive, got ({Ho}, {Wo})")
-    B = max([src.shape[0], _n_cameras(src_camera)] + ([_n_cameras(dst_camera)] if dst_camera is not None else []))
-    if src.shape[0] not in (1, B):
-        raise ValueError(f"{fn}: src of {src.shape[0]} images for a batch of {B} (1 or {B} expected)")
-    if not src.is_cuda:
-        raise RuntimeError(f"{fn}: {_GPU}")
+    Ho, Wo = _args.image_shape(fn, out_shape, "out_shape")
+    B = max([src.shape[0], _args.n_cameras(src_camera)] + ([_args.n_cameras(dst_camera)] if dst_camera is not None else []))
+    _args.batch_of(fn, "src", src.shape[0], B)
+    _args.one_gpu(fn, src.device)
     cam_s = prepare_camera(src_camera, B, src.device)
     if dst_camera is None:
         rows = torch.zeros_like(cam_s.params)
@@ -187,7 +150,7 @@ def undistort(src: torch.Tensor, src_camera, dst_camera=None, out_shape: Optiona
     res = res if return_mask else (res,)
     if return_uv:
         res = res + (uv,)
-    return res if len(res) > 1 else res[0]
+    return _args.tail(res)
 
 
 def overlap_mask(projected: torch.Tensor) -> torch.Tensor:
@@ -195,19 +158,15 @@ def overlap_mask(projected: torch.Tensor) -> torch.Tensor:
     the pixel grid -> bool [B,1,H,W], False where the flow projected - grid, followed a tenth of its way, meets a flow shorter than 0.9 of
     its own (content folded over from another part of the image) and is at least a pixel long.  H, W >= 2.  One launch."""
     fn = "overlap_mask"
-    if not isinstance(projected, torch.Tensor) or not projected.is_floating_point():
-        raise ValueError(f"{fn}: projected must be a float tensor, got {getattr(projected, 'dtype', type(projected).__name__)}")
+    _args.float_tensor(fn, "projected", projected)
     if projected.ndim != 4 or projected.shape[1] != 2 or projected.shape[0] == 0:
         raise ValueError(f"{fn}: projected must be [B,2,H,W], got {tuple(projected.shape)}")
     B, _, H, W = projected.shape
     if H < 2 or W < 2:
         raise ValueError(f"{fn}: H and W must be at least 2 (the sample grid divides by H - 1 and W - 1), got ({H}, {W})")
-    if B > _lib.UD_RECON_MAX_B:
-        raise ValueError(f"{fn}: at most {_lib.UD_RECON_MAX_B} images per call, got {B}")
-    if H * W >= 2 ** 31 - 256:
-        raise ValueError(f"{fn}: unsupported sizes H={H} W={W}")
-    if not projected.is_cuda:
-        raise RuntimeError(f"{fn}: {_GPU}")
+    _args.max_images(fn, B)
+    _args.max_elems(fn, f"H={H} W={W}", H * W)
+    _args.one_gpu(fn, projected.device)
     with torch.cuda.device(projected.device):
         uv = projected.float().contiguous()
         mask = torch.empty((B, 1, H, W), device=uv.device, dtype=torch.uint8)

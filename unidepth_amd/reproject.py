@@ -19,7 +19,8 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _args, _lib
+from .gtpoints import prepare_camera
 from .ops import check, cur_stream, mk
 from .pointcloud import PointCloud
 
@@ -34,29 +35,12 @@ class RenderedView:
     count: Optional[torch.Tensor] = None
 
 
-def _matrices(fn, name, m, B, rows, cols):
-    """fp32 [rows,cols], [1,rows,cols] or [B,rows,cols] -> contiguous [n,rows,cols]."""
-    if not isinstance(m, torch.Tensor) or m.dtype != torch.float32 or tuple(m.shape) not in ((rows, cols), (1, rows, cols), (B, rows, cols)):
-        raise ValueError(f"{fn}: {name} must be fp32 [{rows},{cols}], [1,{rows},{cols}] or [{B},{rows},{cols}]")
-    return m.reshape(-1, rows, cols).contiguous()
-
-
-def _image_shape(fn, image_shape):
-    try:
-        H, W = (int(v) for v in image_shape)
-    except (TypeError, ValueError):
-        raise ValueError(f"{fn}: image_shape must be (H, W)") from None
-    if H <= 0 or W <= 0:
-        raise ValueError(f"{fn}: image_shape must be positive, got ({H}, {W})")
-    return H, W
-
-
 def _render(fn, points, image_shape, projector, transform, image, mode, pixel_offset, rounding, depth_range, return_index, return_count,
             workspace, flags=0) -> RenderedView:
     """What render_depth and render_depth_camera share: the parsing of every argument but the projector's, the workspace, the outputs and
     the call.  projector(B, device) -> (descriptor class, entry point's name, {tensors of the projector}, {its other fields},
-    [(index, value) of the descriptor's model array])."""
-    H, W = _image_shape(fn, image_shape)
+    the PreparedCamera whose model tags the descriptor takes, or None)."""
+    H, W = _args.image_shape(fn, image_shape)
     offsets = None
     if isinstance(points, PointCloud):
         xyz, offsets = points.xyz, points.offsets
@@ -72,14 +56,7 @@ def _render(fn, points, image_shape, projector, transform, image, mode, pixel_of
     else:
         if not isinstance(points, torch.Tensor) or points.dtype != torch.float32:
             raise ValueError(f"{fn}: points must be an fp32 tensor or a PointCloud")
-        if points.ndim == 4 and points.shape[1] == 3:
-            B, n = points.shape[0], points.shape[2] * points.shape[3]
-            strides = (3 * n, 1, n)
-        elif points.ndim == 3 and points.shape[2] == 3:
-            B, n = points.shape[0], points.shape[1]
-            strides = (3 * n, 3, 1)
-        else:
-            raise ValueError(f"{fn}: points must be [B,3,h,w] or [B,N,3], got {tuple(points.shape)}")
+        B, n, _, _, strides = _args.layout(fn, "points", points, 3)
         if B <= 0:
             raise ValueError(f"{fn}: empty batch")
         xyz, cshape = points.contiguous(), tuple(points.shape)
@@ -87,16 +64,13 @@ def _render(fn, points, image_shape, projector, transform, image, mode, pixel_of
         raise ValueError(f"{fn}: mode must be 'nearest' or 'mean', got {mode!r}")
     if rounding not in ("floor", "trunc"):
         raise ValueError(f"{fn}: rounding must be 'floor' or 'trunc', got {rounding!r}")
-    desc_cls, entry, proj_tensors, proj_fields, models = projector(B, xyz.device)
+    desc_cls, entry, proj_tensors, proj_fields, cam = projector(B, xyz.device)
     tensors = {"xyz": xyz, **proj_tensors}
     if offsets is not None:
         tensors["offsets"] = offsets
-    nT = 0
-    if transform is not None:
-        if isinstance(transform, torch.Tensor) and transform.shape[-2:] == (4, 4):
-            transform = transform[..., :3, :]
-        tensors["T"] = _matrices(fn, "transform", transform, B, 3, 4)
-        nT = tensors["T"].shape[0]
+    T, nT = _args.rigid(fn, transform, B)
+    if T is not None:
+        tensors["T"] = T
     if image is not None:
         if mode == "mean":
             raise ValueError(f"{fn}: image needs mode='nearest' (a mean has no winning point to take a colour from)")
@@ -139,8 +113,8 @@ def _render(fn, points, image_shape, projector, transform, image, mode, pixel_of
                nT=nT, mode=_lib.UD_SPLAT_MEAN if mode == "mean" else _lib.UD_SPLAT_NEAREST, flags=flags,
                color_f32=int(image is not None and image.dtype == torch.float32), pixel_offset=float(pixel_offset), dmin=dmin, dmax=dmax,
                **proj_fields, **tensors)
-        for b, m in models:
-            d.model[b] = m
+        if cam is not None:
+            _args.set_models(d.model, cam)
         check(getattr(_lib.lib, entry)(d, cur_stream()), entry)
     return RenderedView(depth, rgb, index, count)
 
@@ -172,15 +146,14 @@ def render_depth(points, intrinsics: torch.Tensor, image_shape: Tuple[int, int],
     fn = "render_depth"
 
     def projector(B, dev):
-        K = _matrices(fn, "intrinsics", intrinsics, B, 3, 3)
-        return _lib.UdSplat, "ud_splat", {"K": K}, {"nK": K.shape[0]}, ()
+        K = _args.matrices(fn, "intrinsics", intrinsics, B, 3, 3)
+        return _lib.UdSplat, "ud_splat", {"K": K}, {"nK": K.shape[0]}, None
     return _render(fn, points, image_shape, projector, transform, image, mode, pixel_offset, rounding, depth_range, return_index,
                    return_count, workspace)
 
 
 def _camera_rows(fn, camera, B, dev):
     """prepare_camera for the projecting functions: a CPU batch is refused here, in this module's words."""
-    from .gtpoints import prepare_camera
     if dev.type != "cuda":
         raise ValueError(f"{fn}: points must live on the GPU; there is no CPU path")
     cam = prepare_camera(camera, B, dev)
@@ -215,7 +188,7 @@ def render_depth_camera(points, camera, image_shape: Tuple[int, int], *, transfo
 
     def projector(B, dev):
         cam = _camera_rows(fn, camera, B, dev)
-        return _lib.UdSplatCamera, "ud_splat_camera", {"params": cam.params}, {"cos_limit": cos_limit}, tuple(enumerate(cam.models))
+        return _lib.UdSplatCamera, "ud_splat_camera", {"params": cam.params}, {"cos_limit": cos_limit}, cam
     return _render(fn, points, image_shape, projector, transform, image, mode, pixel_offset, rounding, depth_range, return_index,
                    return_count, workspace, flags)
 
@@ -235,19 +208,12 @@ def project_camera(points: torch.Tensor, camera, image_shape: Optional[Tuple[int
     fn = "project_camera"
     if not isinstance(points, torch.Tensor) or points.dtype != torch.float32:
         raise ValueError(f"{fn}: points must be an fp32 tensor")
-    if points.ndim == 4 and points.shape[1] == 3:
-        B, n = points.shape[0], points.shape[2] * points.shape[3]
-        strides, rows, tail = (3 * n, 1, n), 0, tuple(points.shape[2:])
-        if image_shape is None:
-            image_shape = tail
-    elif points.ndim == 3 and points.shape[2] == 3:
-        B, n = points.shape[0], points.shape[1]
-        strides, rows, tail = (3 * n, 3, 1), 1, (n,)
-        if image_shape is None:
+    B, n, tail, rows, strides = _args.layout(fn, "points", points, 3)
+    if image_shape is None:
+        if rows:
             raise ValueError(f"{fn}: image_shape is required for [B,N,3] points")
-    else:
-        raise ValueError(f"{fn}: points must be [B,3,h,w] or [B,N,3], got {tuple(points.shape)}")
-    H, W = _image_shape(fn, image_shape)
+        image_shape = tail
+    H, W = _args.image_shape(fn, image_shape)
     if B <= 0:
         raise ValueError(f"{fn}: empty batch")
     if n > 2 ** 31 - 1:
@@ -255,14 +221,9 @@ def project_camera(points: torch.Tensor, camera, image_shape: Optional[Tuple[int
     dev = points.device
     cam = _camera_rows(fn, camera, B, dev)
     xyz = points.contiguous()
-    T, nT = None, 0
-    if transform is not None:
-        if isinstance(transform, torch.Tensor) and transform.shape[-2:] == (4, 4):
-            transform = transform[..., :3, :]
-        T = _matrices(fn, "transform", transform, B, 3, 4)
-        if T.device != dev:
-            raise ValueError(f"{fn}: T must live on the GPU of the points ({dev}); there is no CPU path")
-        nT = T.shape[0]
+    T, nT = _args.rigid(fn, transform, B)
+    if T is not None and T.device != dev:
+        raise ValueError(f"{fn}: T must live on the GPU of the points ({dev}); there is no CPU path")
     with torch.cuda.device(dev):
         uv = torch.empty((B, n, 2) if rows else (B, 2) + tail, device=dev, dtype=torch.float32)
         inside = torch.empty((B,) + tail, device=dev, dtype=torch.uint8)
@@ -270,8 +231,7 @@ def project_camera(points: torch.Tensor, camera, image_shape: Optional[Tuple[int
         if n:
             d = mk(_lib.UdCameraProject, xyz=xyz, params=cam.params, T=T, uv=uv, inside=inside, depth=depth, batch_stride=strides[0],
                    point_stride=strides[1], comp_stride=strides[2], n_points=n, B=B, H=H, W=W, nT=nT, uv_rows=rows)
-            for b, m in enumerate(cam.models):
-                d.model[b] = m
+            _args.set_models(d.model, cam)
             check(_lib.lib.ud_camera_project(d, cur_stream()), "ud_camera_project")
     return uv, inside.view(torch.bool), depth
 

@@ -14,81 +14,45 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
-from .cameras import BatchCamera, GT_FISHEYE624, GT_OPENCV, as_camera
-from .gtpoints import PreparedCamera, prepare_camera
+from . import _args, _lib
+from .gtpoints import prepare_camera
 from .ops import check, cur_stream, mk
-
-_GPU = "GPU tensors on one device expected (the HIP kernels are the only implementation)"
-
-
-def _n_cameras(camera) -> int:
-    if isinstance(camera, PreparedCamera):
-        return len(camera)
-    if isinstance(camera, torch.Tensor):
-        return camera.shape[0] if camera.ndim == 3 else 1
-    cam = as_camera(camera)
-    return len(cam.cameras) if isinstance(cam, BatchCamera) else cam.params.shape[0]
-
-
-def _camera_device(camera):
-    t = camera if isinstance(camera, torch.Tensor) else getattr(camera, "params", None)
-    return t.device if isinstance(t, torch.Tensor) else torch.device("cpu")
 
 
 def _unproject(fn, uv, camera, depth, normalize, image_shape, return_mask, batch=None):
     if normalize and depth is not None:
         raise ValueError(f"{fn}: normalize and depth exclude each other (a depth scales the ray the model's reconstruct rule defines)")
     if image_shape is not None:
-        try:
-            H, W = (int(v) for v in image_shape)
-        except (TypeError, ValueError):
-            raise ValueError(f"{fn}: image_shape must be (H, W)") from None
-        if H <= 0 or W <= 0:
-            raise ValueError(f"{fn}: image_shape must be positive, got ({H}, {W})")
+        H, W = _args.image_shape(fn, image_shape)
     if uv is None:
         if image_shape is None:
             raise ValueError(f"{fn}: uv=None (the identity grid) needs image_shape=(H, W)")
         nb, n, tail, rows, strides = 1, H * W, (H, W), 0, (0, 1, 1)
     else:
-        if not isinstance(uv, torch.Tensor) or not uv.is_floating_point():
-            raise ValueError(f"{fn}: uv must be a float tensor, got {getattr(uv, 'dtype', type(uv).__name__)}")
-        if uv.ndim == 4 and uv.shape[1] == 2:
-            nb, tail, rows = uv.shape[0], tuple(uv.shape[2:]), 0
-            n = tail[0] * tail[1]
-            strides = (2 * n, 1, n)
-        elif uv.ndim == 3 and uv.shape[2] == 2:
-            nb, tail, rows = uv.shape[0], (uv.shape[1],), 1
-            n = tail[0]
-            strides = (2 * n, 2, 1)
-        else:
-            raise ValueError(f"{fn}: uv must be [B,2,H,W] or [B,N,2] (B or 1 images), got {tuple(uv.shape)}")
+        _args.float_tensor(fn, "uv", uv)
+        nb, n, tail, rows, strides = _args.layout(fn, "uv", uv, 2)
         if nb == 0:
             raise ValueError(f"{fn}: empty batch")
         if image_shape is None:
             H, W = tail if not rows else (1, 1)                  # read for the identity grid only
     if depth is not None:
-        if not isinstance(depth, torch.Tensor) or not depth.is_floating_point():
-            raise ValueError(f"{fn}: depth must be a float tensor, got {getattr(depth, 'dtype', type(depth).__name__)}")
+        _args.float_tensor(fn, "depth", depth)
         if depth.ndim == 0 or depth.shape[0] == 0 or depth.numel() != depth.shape[0] * n or \
                 (depth.ndim > 2 and tuple(depth.shape[-2:]) != tail) or (rows and depth.ndim != 2):
             raise ValueError(f"{fn}: depth {tuple(depth.shape)} does not hold one value for each of the {tail} coordinates of every image")
-    sizes = [nb, _n_cameras(camera)] + ([depth.shape[0]] if depth is not None else []) + ([int(batch)] if batch is not None else [])
+    sizes = [nb, _args.n_cameras(camera)] + ([depth.shape[0]] if depth is not None else []) + ([int(batch)] if batch is not None else [])
     B = max(sizes)
-    if uv is not None and nb not in (1, B):
-        raise ValueError(f"{fn}: uv of {nb} images for a batch of {B} (1 or {B} expected)")
-    if depth is not None and depth.shape[0] != B:
-        raise ValueError(f"{fn}: depth of {depth.shape[0]} images for a batch of {B}")
-    if B > _lib.UD_RECON_MAX_B:
-        raise ValueError(f"{fn}: at most {_lib.UD_RECON_MAX_B} images per call, got {B}")
-    if n >= 2 ** 31 - 256:
-        raise ValueError(f"{fn}: unsupported sizes B={B} points={n}")
-    dev = uv.device if uv is not None else depth.device if depth is not None else _camera_device(camera)
+    if uv is not None:
+        _args.batch_of(fn, "uv", nb, B)
+    if depth is not None:
+        _args.batch_of(fn, "depth", depth.shape[0], B, shared=False)
+    _args.max_images(fn, B)
+    _args.max_elems(fn, f"B={B} points={n}", n)
+    dev = uv.device if uv is not None else depth.device if depth is not None else _args.camera_device(camera)
     if dev.type != "cuda" and uv is None and depth is None and torch.cuda.is_available():
         dev = torch.device("cuda", torch.cuda.current_device())         # a host camera object and nothing else: the current GPU
     cam = prepare_camera(camera, B, dev)                                 # raises for a CPU batch
-    if dev.type != "cuda" or cam.params.device != dev or (depth is not None and depth.device != dev):
-        raise RuntimeError(f"{fn}: {_GPU}")
+    _args.one_gpu(fn, dev, cam.params, depth)
     with torch.cuda.device(dev):
         src = None if uv is None else uv.float().contiguous()
         if src is not None and nb == 1:
@@ -96,14 +60,13 @@ def _unproject(fn, uv, camera, depth, normalize, image_shape, return_mask, batch
         d = None if depth is None else depth.reshape(B, n).float().contiguous()
         rays = torch.empty((B, n, 3) if rows else (B, 3) + tail, device=dev, dtype=torch.float32)
         valid = torch.empty((B, n) if rows else (B, 1) + tail, device=dev, dtype=torch.uint8) if return_mask else None
-        n_iter = sum(m in (GT_OPENCV, GT_FISHEYE624) for m in cam.models)
+        n_iter = _args.n_iterative(cam)
         nbytes = int(_lib.lib.ud_camera_unproject_work_bytes(B, n_iter))
         work = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
         desc = mk(_lib.UdCameraUnproject, uv=src, params=cam.params, depth=d, rays=rays, valid=valid, work=work, work_bytes=nbytes,
                   batch_stride=strides[0], point_stride=strides[1], comp_stride=strides[2], n_points=n, B=B, H=H, W=W,
                   normalize=int(bool(normalize)), rays_rows=rows)
-        for b, m in enumerate(cam.models):
-            desc.model[b] = m
+        _args.set_models(desc.model, cam)
         check(_lib.lib.ud_camera_unproject(desc, cur_stream()), "ud_camera_unproject")
     return (rays, valid.view(torch.bool)) if return_mask else rays
 

@@ -9,29 +9,15 @@ destination pixel: the point map, the coordinate map, the inside mask and the pr
 the bits the separate calls give.  The HIP kernel is the only implementation: CPU tensors raise."""
 from __future__ import annotations
 
-import math
-import struct
 from typing import Optional
 
 import torch
 
-from . import _lib
-from .cameras import GT_FISHEYE624, GT_OPENCV
+from . import _args, _lib
+from .gtpoints import PreparedCamera, prepare_camera
 from .ops import check, cur_stream, mk
-from .remap import _GPU, _MODES, _PADDINGS
-
-_ITERATIVE = (GT_OPENCV, GT_FISHEYE624)
-
-
-def _source_map(fn, name, t, Hs, Ws, float_ok):
-    """[B or 1,1,Hs,Ws] / [.,Hs,Ws] of the source view: a mask (bool / uint8) or a depth (any float dtype) -> its batch"""
-    kind = "a float" if float_ok else "a bool or uint8"
-    good = isinstance(t, torch.Tensor) and (t.is_floating_point() if float_ok else t.dtype in (torch.bool, torch.uint8))
-    if not good:
-        raise ValueError(f"{fn}: {name} must be {kind} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if t.ndim not in (3, 4) or t.shape[0] == 0 or tuple(t.shape[-2:]) != (Hs, Ws) or t.numel() != t.shape[0] * Hs * Ws:
-        raise ValueError(f"{fn}: {name} {tuple(t.shape)} is not [B,1,{Hs},{Ws}] (B or 1 images)")
-    return t.shape[0]
+from .remap import _MODES, _PADDINGS
+from .unproject import unproject_camera
 
 
 def warp_camera(src: torch.Tensor, *, depth: Optional[torch.Tensor] = None, camera=None, points: Optional[torch.Tensor] = None, src_camera,
@@ -74,9 +60,6 @@ def warp_camera(src: torch.Tensor, *, depth: Optional[torch.Tensor] = None, came
     the points of the whole batch come from unproject_camera first and `depth > 0` is ANDed into valid_in: five launches (three of
     unproject_camera, one comparison, the warp), six with a valid_in.  Stream-ordered, nothing synchronises, no workspace: captures into
     a graph (with PreparedCamera cameras)."""
-    from .gtpoints import PreparedCamera, prepare_camera
-    from .reproject import _matrices
-    from .unproject import _n_cameras, unproject_camera
     fn = "warp_camera"
     if mode not in _MODES:
         raise ValueError(f"{fn}: mode must be one of {tuple(_MODES)}, got {mode!r}")
@@ -99,72 +82,42 @@ def warp_camera(src: torch.Tensor, *, depth: Optional[torch.Tensor] = None, came
     if depth is not None:
         if camera is None:
             raise ValueError(f"{fn}: depth needs camera, the destination view's camera")
-        if not isinstance(depth, torch.Tensor) or not depth.is_floating_point():
-            raise ValueError(f"{fn}: depth must be a float tensor, got {getattr(depth, 'dtype', type(depth).__name__)}")
-        if depth.ndim not in (3, 4) or (depth.ndim == 4 and depth.shape[1] != 1) or min(depth.shape) == 0:
-            raise ValueError(f"{fn}: depth must be [B,1,Ho,Wo] or [B,Ho,Wo], non-empty, got {tuple(depth.shape)}")
-        B, (Ho, Wo) = depth.shape[0], depth.shape[-2:]
+        B, Ho, Wo = _args.depth_map(fn, "depth", depth)
     else:
         if camera is not None:
             raise ValueError(f"{fn}: camera goes with depth; points are already in the destination camera's frame")
-        if not isinstance(points, torch.Tensor) or not points.is_floating_point():
-            raise ValueError(f"{fn}: points must be a float tensor, got {getattr(points, 'dtype', type(points).__name__)}")
-        if points.ndim != 4 or points.shape[1] != 3 or min(points.shape) == 0:
-            raise ValueError(f"{fn}: points must be [B,3,Ho,Wo], non-empty, got {tuple(points.shape)}")
-        B, (Ho, Wo) = points.shape[0], points.shape[-2:]
+        B, Ho, Wo = _args.point_map(fn, "points", points)
     n = Ho * Wo
     sizes = {"src": sb}
     if src_mask is not None:
-        sizes["src_mask"] = _source_map(fn, "src_mask", src_mask, Hs, Ws, False)
+        sizes["src_mask"] = _args.image_map(fn, "src_mask", src_mask, Hs, Ws, mask=True)
     if (src_depth is None) != (occlusion_tol is None):
         raise ValueError(f"{fn}: src_depth and occlusion_tol come together or not at all")
-    tol, tol_bits = 0.0, 0
+    tol_bits = 0
     if src_depth is not None:
-        sizes["src_depth"] = _source_map(fn, "src_depth", src_depth, Hs, Ws, True)
-        try:
-            tol = float(occlusion_tol)
-            tol_bits = struct.unpack("<i", struct.pack("<f", tol))[0]                 # the descriptor carries the fp32's bit pattern
-        except (TypeError, ValueError, OverflowError):
-            raise ValueError(f"{fn}: occlusion_tol must be a number in fp32's range") from None
-        if not (tol >= 0.0 and math.isfinite(tol)):
-            raise ValueError(f"{fn}: occlusion_tol must be finite and not negative, got {tol}")
+        sizes["src_depth"] = _args.image_map(fn, "src_depth", src_depth, Hs, Ws, mask=False)
+        tol_bits = _args.tolerance(fn, "occlusion_tol", occlusion_tol)[1]         # the descriptor carries the fp32's bit pattern
     if valid_in is not None:
-        if not isinstance(valid_in, torch.Tensor) or valid_in.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f"{fn}: valid_in must be a bool or uint8 tensor, got {getattr(valid_in, 'dtype', type(valid_in).__name__)}")
-        if valid_in.ndim not in (3, 4) or valid_in.shape[0] == 0 or tuple(valid_in.shape[-2:]) != (Ho, Wo) or valid_in.numel() != valid_in.shape[0] * n:
-            raise ValueError(f"{fn}: valid_in {tuple(valid_in.shape)} does not hold one value for each of the ({Ho}, {Wo}) pixels of every image")
-        sizes["valid_in"] = valid_in.shape[0]
+        sizes["valid_in"] = _args.image_map(fn, "valid_in", valid_in, Ho, Wo, mask=True)
     for name, cam in (("camera", camera), ("src_camera", src_camera)):
         if cam is not None:
-            sizes[name] = _n_cameras(cam)
-    for name, k in sizes.items():
-        if k not in (1, B):
-            raise ValueError(f"{fn}: {name} of {k} images for a batch of {B} (1 or {B} expected)")
+            sizes[name] = _args.n_cameras(cam)
+    _args.batches(fn, sizes, B)
     for name, cam in (("camera", camera), ("src_camera", src_camera)):
-        if isinstance(cam, PreparedCamera) and len(cam) != B:
-            raise ValueError(f"{fn}: {name}: a prepared camera of {len(cam)} images for a batch of {B}")
-    if B > _lib.UD_RECON_MAX_B:
-        raise ValueError(f"{fn}: at most {_lib.UD_RECON_MAX_B} images per call, got {B}")
-    if max(n, Cc * n, Cc * Hs * Ws) >= 2 ** 31 - 256:
-        raise ValueError(f"{fn}: unsupported sizes C={Cc} source={Hs}x{Ws} destination={Ho}x{Wo}")
-    T, nT = None, 0
-    if transform is not None:
-        if isinstance(transform, torch.Tensor) and transform.shape[-2:] == (4, 4):
-            transform = transform[..., :3, :]
-        T = _matrices(fn, "transform", transform, B, 3, 4)
-        nT = T.shape[0]
+        if isinstance(cam, PreparedCamera):
+            _args.batch_of(fn, name, len(cam), B, shared=False)
+    _args.max_images(fn, B)
+    _args.max_elems(fn, f"C={Cc} source={Hs}x{Ws} destination={Ho}x{Wo}", n, Cc * n, Cc * Hs * Ws)
+    T, nT = _args.rigid(fn, transform, B)
     dev = src.device
-    others = [t for t in (depth, points, src_mask, valid_in, src_depth, T) if t is not None]
-    others += [c.params for c in (camera, src_camera) if isinstance(c, PreparedCamera)]
-    if dev.type != "cuda" or any(t.device != dev for t in others):
-        raise RuntimeError(f"{fn}: {_GPU}")
+    _args.one_gpu(fn, dev, depth, points, src_mask, valid_in, src_depth, T, *_args.prepared_rows(camera, src_camera))
     with torch.cuda.device(dev):
         cam_s = prepare_camera(src_camera, B, dev)
         cam_d = None
         if depth is not None:
             cam_d = prepare_camera(camera, B, dev)
             d = depth.reshape(B, n).float().contiguous()
-            if any(m in _ITERATIVE for m in cam_d.models):          # not fused: the radial loop ends on a maximum over the image
+            if _args.n_iterative(cam_d):                            # not fused: the radial loop ends on a maximum over the image
                 points = unproject_camera(None, cam_d, depth=d.view(B, Ho, Wo), image_shape=(Ho, Wo))
                 positive = (d > 0).view(B, Ho, Wo)
                 valid_in = positive if valid_in is None else positive & valid_in.reshape(-1, Ho, Wo).bool()
@@ -190,10 +143,9 @@ def warp_camera(src: torch.Tensor, *, depth: Optional[torch.Tensor] = None, came
                   normalize=int(bool(normalize)), src_u8=int(src_u8), out_u8=int(out_dtype == torch.uint8), src_shared=int(sb == 1),
                   mask_shared=int(m is not None and m.shape[0] == 1), depth_shared=int(sd is not None and sd.shape[0] == 1),
                   tol_bits=tol_bits)
-        for b in range(B):
-            desc.model_src[b] = cam_s.models[b]
-            if cam_d is not None:
-                desc.model_dst[b] = cam_d.models[b]
+        _args.set_models(desc.model_src, cam_s)
+        if cam_d is not None:
+            _args.set_models(desc.model_dst, cam_d)
         check(_lib.lib.ud_warp_camera(desc, cur_stream()), "ud_warp_camera")
     res = (out,)
     if return_mask:
@@ -204,4 +156,4 @@ def warp_camera(src: torch.Tensor, *, depth: Optional[torch.Tensor] = None, came
         res += (uv,)
     if return_depth:
         res += (pd,)
-    return res if len(res) > 1 else res[0]
+    return _args.tail(res)
