@@ -781,6 +781,64 @@ typedef struct UdDepthConsistency {
 } UdDepthConsistency;
 int ud_depth_consistency(const UdDepthConsistency* desc, void* stream);
 
+/* Depth views fused into a truncated signed distance (TSDF) volume in ONE launch (csrc/tsdf.hip; the arithmetic of a voxel is
+ * csrc/tsdf_point.h, which only calls csrc/camera_models.h and csrc/remap_taps.h): every voxel centre is projected into every view, the
+ * view's depth is read at the nearest pixel and the truncated distance is averaged into the voxel, one thread per voxel with the view loop
+ * inside it.  Per view it is ud_camera_project -> ud_remap (nearest) and the element-wise update fused; every output has the bits the
+ * separate calls give.  No workspace, no atomics, no LDS, no host synchronisation: captures into a graph.
+ *   Volume b: tsdf, weight fp32 [B,Nz,Ny,Nx] (x fastest), color fp32 planar [B,3,Nz,Ny,Nx] (with image, else NULL), count uint8
+ *     [B,Nz,Ny,Nx] (optional: the views that updated the voxel in this call).  Voxel i = (iz * Ny + iy) * Nx + ix has the centre
+ *     p = origin + ((float)index + 0.5f) * voxel_size per axis, origin fp32 [n_origin,3], n_origin = 1 (shared) or B.
+ *     fresh != 0: the state starts at tsdf = 1, weight = 0, color = 0 and the volume's memory is not read; otherwise it is read.
+ *   View v = 0 .. V-1, in this order: src_depth fp32 [B,V,Hs,Ws], src_mask uint8 [B,V,Hs,Ws] (optional), src_weight fp32 [B,V,Hs,Ws]
+ *     (optional), image uint8 [B,V,3,Hs,Ws] (optional), params fp32 [V,B,16], model[v * B + b]; T fp32 [nT,V,3,4] (nT = 1 or B sets of V
+ *     matrices): volume (world) to view-camera coordinates, ud_camera_project's arithmetic.
+ *       q = T p; (u, w) = the view's projection of q, d its depth, inside its in-image test against (Hs, Ws).
+ *       One nearest tap at (u, w), zeros padding (csrc/remap_taps.h); it contributes when src_depth there is > 0 and src_mask != 0.
+ *       valid = inside && u, w finite && 0 <= u <= Ws && 0 <= w <= Hs && the tap contributes (UdRemap's valid for coord_valid = inside and
+ *         src_mask = (src_depth > 0) & src_mask).  ds = the depth at the tap, wv = src_weight there (1 without), rgb = image's bytes there.
+ *       sdf = ds - d; obs = valid && d > 0 && sdf >= -trunc && wv > 0 && wv <= FLT_MAX (false whenever a NaN is involved);
+ *       s = fminf(sdf / trunc, 1).  If obs: Wn = weight + wv; tsdf = (tsdf * weight + s * wv) / Wn; color[k] = (color[k] * weight + rgb[k]
+ *         * wv) / Wn; weight = has_max_weight ? fminf(Wn, max_weight) : Wn; ++count.  Every operation rounded separately in fp32.
+ *   voxel_size_bits / trunc_bits / max_weight_bits hold the bit patterns of the fp32 values (the descriptor has integer and pointer fields
+ *   only).  All six camera models (projection is closed form for each).  A coordinate never becomes an address before it is safe.
+ *   Limits: B, V >= 1, B * V <= UD_RECON_MAX_B, V <= 255, Nx, Ny, Nz, Hs, Ws >= 1; Nx * Ny * Nz, Hs * Ws, V * 3 * Hs * Ws < 2^31 - 256; nT
+ *   and n_origin 1 or B; voxel_size, trunc finite and > 0; max_weight finite and > 0 when has_max_weight != 0; image and color both or
+ *   neither.  Every refusal is returned before any HIP call.  Built with -ffp-contract=off. */
+typedef struct UdTsdfIntegrate {
+  const float* src_depth; const unsigned char* src_mask; const float* src_weight; const unsigned char* image;
+  const float* params; const float* T; const float* origin;
+  float* tsdf; float* weight; float* color; unsigned char* count;
+  int B, V, Nx, Ny, Nz, Hs, Ws, nT, n_origin, fresh, has_max_weight, voxel_size_bits, trunc_bits, max_weight_bits;
+  unsigned char model[UD_RECON_MAX_B];
+} UdTsdfIntegrate;
+int ud_tsdf_integrate(const UdTsdfIntegrate* desc, void* stream);
+
+/* The surface of a TSDF volume as packed points (csrc/tsdf.hip): UdPointCloud's ordered, deterministic compaction (flag + count, scan,
+ * pack; no atomics, no host synchronisation) over SLOTS instead of pixels.  Slot s = 3 * voxel + axis of volume b is the edge from the
+ * voxel to its +x (axis 0) / +y (1) / +z (2) neighbour.  It is live when the neighbour lies in the grid, both weights are >= min_weight,
+ * a = tsdf[voxel] and b = tsdf[neighbour] are both not NaN and (a < 0) != (b < 0).  Its row: t = a / (a - b); xyz = the voxel's centre
+ * (UdTsdfIntegrate's) with coordinate [axis] moved by t * voxel_size; colour c0[k] + t * (c1[k] - c0[k]), stored as fp32 (rgb_f32 != 0) or
+ * rounded half to even and clamped to a byte.  Every operation rounded separately in fp32.
+ *   inputs: tsdf, weight fp32 [B,Nz,Ny,Nx]; color fp32 [B,3,Nz,Ny,Nx] or NULL; origin fp32 [n_origin,3], n_origin = 1 or B.
+ *   Order: volumes in batch order, slots ascending inside a volume.  Bitwise reproducible.
+ *   outputs: counts int64 [B] and offsets int64 [B+1] are always written, with the TRUE totals whatever `capacity` is.  xyz == NULL: count
+ *     only.  Otherwise, for the rows r < min(total, capacity): xyz fp32 [capacity,3]; rgb [capacity,3] u8 or fp32 (optional, needs color).
+ *     Rows r >= capacity are dropped, rows r >= total never written.
+ *   work: device scratch of at least ud_tsdf_points_work_bytes(B, Nx, Ny, Nz) bytes (host-only query; -1 outside the limits), 8-byte
+ *     aligned, work_bytes its size.  Its contents need no initialisation.
+ *   Limits: 1 <= B <= 65535, Nx, Ny, Nz >= 1, 3 * Nx * Ny * Nz < 2^31 - 256, capacity >= 0, voxel_size finite and > 0, min_weight not a
+ *   NaN.  Every refusal is returned before any HIP call.  Built with -ffp-contract=off. */
+typedef struct UdTsdfPoints {
+  const float* tsdf; const float* weight; const float* color; const float* origin;
+  float* xyz; void* rgb; long long* counts; long long* offsets;
+  void* work; long long work_bytes;
+  long long capacity;
+  int B, Nx, Ny, Nz, n_origin, rgb_f32, voxel_size_bits, min_weight_bits;
+} UdTsdfPoints;
+int ud_tsdf_points(const UdTsdfPoints* desc, void* stream);
+long long ud_tsdf_points_work_bytes(int B, int Nx, int Ny, int Nz);
+
 /* Surface normals of a point map, or of a depth map seen through a camera, in ONE launch (csrc/normals.hip; the arithmetic of a pixel is
  * csrc/normals_point.h, where the definition is written out operation by operation).  Exactly one of:
  *     points fp32 planar [B,3,H,W]: the points form.  depth fp32 [B,H,W] is optional there and only feeds the edge test (P.z otherwise).
@@ -1131,7 +1189,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41; 16, 19, 22, 24, 26, 30, 32, 35, 37 and 40 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41, UdTsdfIntegrate = 43, UdTsdfPoints = 44; 16, 19, 22, 24, 26, 30, 32, 35, 37, 40 and 42 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

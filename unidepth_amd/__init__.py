@@ -18,8 +18,9 @@ _REMAP = ("remap", "undistort", "overlap_mask")
 _WARP = ("warp_camera",)
 _NORMALS = ("normals_from_points", "normals_camera", "eval_normals")
 _CONSISTENCY = ("depth_consistency", "depth_consistency_composition", "invert_rigid")
+_TSDF = ("TsdfVolume", "tsdf_integrate", "tsdf_integrate_composition", "tsdf_points")
 __all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP, *_WARP, *_NORMALS,
-           *_CONSISTENCY]
+           *_CONSISTENCY, *_TSDF]
 
 
 def __getattr__(name):
@@ -62,4 +63,7 @@ def __getattr__(name):
     if name in _CONSISTENCY:                          # multi-view depth check and fusion in one launch (consistency.py, csrc/consistency.hip)
         from . import consistency
         return getattr(consistency, name)
+    if name in _TSDF:                                 # depth views fused into a TSDF volume, and its surface as points (tsdf.py, csrc/tsdf.hip)
+        from . import tsdf
+        return getattr(tsdf, name)
     raise AttributeError(name)

@@ -159,6 +159,21 @@ class UdDepthConsistency(C.Structure):
                 ("px_tol_bits", i32), ("rel_tol_bits", i32), ("model_ref", C.c_ubyte * UD_RECON_MAX_B), ("model_src", C.c_ubyte * UD_RECON_MAX_B)]
 
 
+class UdTsdfIntegrate(C.Structure):
+    _fields_ = [("src_depth", vp), ("src_mask", vp), ("src_weight", vp), ("image", vp), ("params", vp), ("T", vp), ("origin", vp),
+                ("tsdf", vp), ("weight", vp), ("color", vp), ("count", vp),
+                ("B", i32), ("V", i32), ("Nx", i32), ("Ny", i32), ("Nz", i32), ("Hs", i32), ("Ws", i32), ("nT", i32), ("n_origin", i32),
+                ("fresh", i32), ("has_max_weight", i32), ("voxel_size_bits", i32), ("trunc_bits", i32), ("max_weight_bits", i32),
+                ("model", C.c_ubyte * UD_RECON_MAX_B)]
+
+
+class UdTsdfPoints(C.Structure):
+    _fields_ = [("tsdf", vp), ("weight", vp), ("color", vp), ("origin", vp), ("xyz", vp), ("rgb", vp), ("counts", vp), ("offsets", vp),
+                ("work", vp), ("work_bytes", i64), ("capacity", i64),
+                ("B", i32), ("Nx", i32), ("Ny", i32), ("Nz", i32), ("n_origin", i32), ("rgb_f32", i32), ("voxel_size_bits", i32),
+                ("min_weight_bits", i32)]
+
+
 UD_EVAL_NORMALS_MAX_T = 8
 
 
@@ -364,6 +379,8 @@ def _load():
         "ud_warp_camera": [P(UdWarpCamera), vp],
         "ud_normals": [P(UdNormals), vp],
         "ud_depth_consistency": [P(UdDepthConsistency), vp],
+        "ud_tsdf_integrate": [P(UdTsdfIntegrate), vp],
+        "ud_tsdf_points": [P(UdTsdfPoints), vp],
         "ud_eval_normals": [P(UdEvalNormals), vp, i64, vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
@@ -393,12 +410,14 @@ def _load():
     lib.ud_camera_unproject_work_bytes.restype = i64
     lib.ud_pointcloud_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_pointcloud_work_bytes.restype = i64
+    lib.ud_tsdf_points_work_bytes.argtypes = [i32, i32, i32, i32]
+    lib.ud_tsdf_points_work_bytes.restype = i64
     lib.ud_colorize_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency]):
-        if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35, 37 and 40 are not assigned: the library answers -1
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency, None, UdTsdfIntegrate, UdTsdfPoints]):
+        if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35, 37, 40 and 42 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

@@ -58,6 +58,9 @@ done
 # (consistency_point.h calls camera_models.h and remap_taps.h); each output must have the bits of those launches run one after the other,
 # same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c consistency.hip -o $BD/consistency.o ) & pids+=($!)
+# tsdf: project, the nearest-pixel remap and the running weighted mean fused per voxel over all views (tsdf_point.h calls camera_models.h
+# and remap_taps.h); the volume must have the bits of those launches run one after the other, same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c tsdf.hip -o $BD/tsdf.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)

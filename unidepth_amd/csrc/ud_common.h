@@ -80,7 +80,7 @@ __device__ __forceinline__ float ud_wave_sum(float v) {
 
 void ud_set_error(const char* msg);
 
-// ---- host side of the camera-map entry points (reconstruct, project, unproject, splat, remap, warp, normals, consistency): the small
+// ---- host side of the camera-map entry points (reconstruct, project, unproject, splat, remap, warp, normals, consistency, tsdf): the small
 // checks each of them makes before its launch
 constexpr long long UD_MAX_ELEMS = 0x7fffffffLL - 256;     // element counts of one image stay below 2^31 - 256
 static inline float ud_f32_from_bits(int bits) {           // the fp32 a descriptor carries as its bit pattern

@@ -1,0 +1,335 @@
+"""Depth views fused into a truncated signed distance (TSDF) volume and the volume's surface read back as points: the step after
+depth_consistency when N predicted depth maps, their cameras and their poses become one scene (the result feeds save_ply).
+
+    TsdfVolume                              tsdf, weight, optional colour, origin and voxel size of a batch of dense voxel grids
+    tsdf_integrate(volume, depths, ...)     one ud_tsdf_integrate call (csrc/tsdf.hip): every voxel against every view, any camera model
+    tsdf_integrate_composition(...)         the same definition spelled per view with project_camera, remap(mode="nearest") and torch
+    tsdf_points(volume, ...)                the zero crossings between neighbouring voxels as a PointCloud (ud_tsdf_points)
+
+For every voxel and every view, in view order: the voxel's centre moved into the view and projected, the view's depth read at the nearest
+pixel, sdf = that depth - the centre's own depth, and where the pixel is valid and the voxel not further than `trunc` behind the surface,
+min(sdf / trunc, 1) averaged into the voxel with the pixel's weight.  The fused kernel keeps the voxel's state in registers across all
+views and every intermediate map out of memory; every output has the bits the composition gives.  The HIP kernels are the only
+implementation of the fused form: CPU tensors raise.  Sequences longer than 256 image-view pairs are integrated by repeated calls on the
+same volume (integrating views in one call or in several gives the same bits)."""
+from __future__ import annotations
+
+import math
+import struct
+from typing import Optional, Sequence
+
+import torch
+
+from . import _args, _lib
+from .gtpoints import PreparedCamera, prepare_camera
+from .ops import check, cur_stream, mk
+from .pointcloud import PointCloud
+from .remap import remap
+from .reproject import project_camera
+
+_FLT_MAX = 3.4028234663852886e38
+
+
+class TsdfVolume:
+    """A batch of B dense voxel grids of (Nz, Ny, Nx) voxels, x fastest: tsdf fp32 [B,Nz,Ny,Nx] (1 where nothing was seen), weight fp32
+    [B,Nz,Ny,Nx] (0 there), color fp32 [B,3,Nz,Ny,Nx] or None, origin fp32 [1 or B,3] (the grid's corner in the volume's frame; the centre
+    of voxel (ix, iy, iz) is origin + (index + 0.5) * voxel_size per axis) and voxel_size (a Python float, exactly representable in fp32)."""
+
+    def __init__(self, tsdf: torch.Tensor, weight: torch.Tensor, color: Optional[torch.Tensor], origin: torch.Tensor, voxel_size: float):
+        self.tsdf, self.weight, self.color, self.origin, self.voxel_size = tsdf, weight, color, origin, voxel_size
+
+
+def _positive(fn, name, x):
+    """a Python number as (the value of its fp32 rounding, that rounding's bit pattern); the rounded value is finite and > 0"""
+    try:
+        bits = _args.f32_bits(float(x))
+    except (TypeError, ValueError, OverflowError, struct.error):
+        raise ValueError(f"{fn}: {name} must be a number in fp32's range") from None
+    val = struct.unpack("<f", struct.pack("<i", bits))[0]
+    if isinstance(x, bool) or not (val > 0.0 and math.isfinite(val)):
+        raise ValueError(f"{fn}: {name} must be finite and positive, got {x}")
+    return val, bits
+
+
+def _check_volume(fn, volume):
+    """a TsdfVolume whose tensors are contiguous fp32 on one GPU and fit each other -> (B, Nz, Ny, Nx, voxel size, its bits)"""
+    if not isinstance(volume, TsdfVolume):
+        raise ValueError(f"{fn}: volume must be a TsdfVolume, got {type(volume).__name__}")
+    t = volume.tsdf
+    ok = lambda x: isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.device == t.device  # noqa: E731
+    if not isinstance(t, torch.Tensor) or t.ndim != 4 or min(t.shape) == 0 or not ok(t):
+        raise ValueError(f"{fn}: volume.tsdf must be a contiguous fp32 GPU tensor [B,Nz,Ny,Nx], non-empty")
+    B, Nz, Ny, Nx = t.shape
+    if not ok(volume.weight) or volume.weight.shape != t.shape:
+        raise ValueError(f"{fn}: volume.weight must be a contiguous fp32 GPU tensor shaped like volume.tsdf {tuple(t.shape)}")
+    if volume.color is not None and (not ok(volume.color) or tuple(volume.color.shape) != (B, 3, Nz, Ny, Nx)):
+        raise ValueError(f"{fn}: volume.color must be None or a contiguous fp32 GPU tensor [{B},3,{Nz},{Ny},{Nx}]")
+    if not ok(volume.origin) or tuple(volume.origin.shape) not in ((1, 3), (B, 3)):
+        raise ValueError(f"{fn}: volume.origin must be a contiguous fp32 GPU tensor [1,3] or [{B},3]")
+    vs, vs_bits = _positive(fn, "volume.voxel_size", volume.voxel_size)
+    return B, Nz, Ny, Nx, vs, vs_bits
+
+
+def _arguments(fn, volume, depths, cameras, transforms, grid_shape, origin, voxel_size, trunc, src_masks, src_weights, images, max_weight):
+    """every check both functions share -> the sizes, the scalars and the tensors in the layout of the descriptor"""
+    _args.float_tensor(fn, "depths", depths)
+    if depths.ndim != 4 or min(depths.shape) == 0:
+        raise ValueError(f"{fn}: depths must be [B,V,Hs,Ws], non-empty, got {tuple(depths.shape)}")
+    B, V, Hs, Ws = depths.shape
+    if V > 255 or B * V > _lib.UD_RECON_MAX_B:
+        raise ValueError(f"{fn}: depths: at most 255 views and {_lib.UD_RECON_MAX_B} image-view pairs per call, got B={B} V={V}")
+    if isinstance(cameras, (torch.Tensor, PreparedCamera)) or not isinstance(cameras, Sequence) or len(cameras) != V:
+        raise ValueError(f"{fn}: cameras must be a sequence of {V} cameras, one per view")
+    for v, cam in enumerate(cameras):
+        _args.batch_of(fn, f"cameras[{v}]", _args.n_cameras(cam), B, shared=not isinstance(cam, PreparedCamera))
+    shapes = ((V, 4, 4), (V, 3, 4), (B, V, 4, 4), (B, V, 3, 4))
+    if not isinstance(transforms, torch.Tensor) or transforms.dtype != torch.float32 or tuple(transforms.shape) not in shapes:
+        raise ValueError(f"{fn}: transforms must be fp32 [{V},4,4], [{B},{V},4,4] or the 3x4 forms of either")
+    tr, tr_bits = _positive(fn, "trunc", trunc)
+    has_max = max_weight is not None
+    mw, mw_bits = _positive(fn, "max_weight", max_weight) if has_max else (0.0, 0)
+    if src_masks is not None:
+        _args.mask_tensor(fn, "src_masks", src_masks)
+        if tuple(src_masks.shape) != (B, V, Hs, Ws):
+            raise ValueError(f"{fn}: src_masks {tuple(src_masks.shape)} is not [{B},{V},{Hs},{Ws}]")
+    if src_weights is not None:
+        _args.float_tensor(fn, "src_weights", src_weights)
+        if tuple(src_weights.shape) != (B, V, Hs, Ws):
+            raise ValueError(f"{fn}: src_weights {tuple(src_weights.shape)} is not [{B},{V},{Hs},{Ws}]")
+    if images is not None and (not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or tuple(images.shape) != (B, V, 3, Hs, Ws)):
+        raise ValueError(f"{fn}: images must be uint8 [{B},{V},3,{Hs},{Ws}]")
+    dev = depths.device
+    fresh = volume is None
+    if fresh:
+        try:
+            Nz, Ny, Nx = (int(k) for k in grid_shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"{fn}: grid_shape must be (Nz, Ny, Nx) when no volume is given") from None
+        if min(Nz, Ny, Nx) < 1:
+            raise ValueError(f"{fn}: grid_shape must be positive, got ({Nz}, {Ny}, {Nx})")
+        vs, vs_bits = _positive(fn, "voxel_size", voxel_size)
+        if isinstance(origin, torch.Tensor):
+            if origin.dtype != torch.float32 or tuple(origin.shape) not in ((3,), (1, 3), (B, 3)):
+                raise ValueError(f"{fn}: origin must be fp32 [3], [1,3] or [{B},3], or three numbers")
+        else:
+            try:
+                origin = torch.tensor([float(k) for k in origin], dtype=torch.float32)
+            except (TypeError, ValueError):
+                origin = None
+            if origin is None or origin.shape != (3,):
+                raise ValueError(f"{fn}: origin must be fp32 [3], [1,3] or [{B},3], or three numbers")
+    else:
+        if grid_shape is not None or origin is not None or voxel_size is not None:
+            raise ValueError(f"{fn}: grid_shape, origin and voxel_size describe a fresh volume; a given volume carries its own")
+        vb, Nz, Ny, Nx, vs, vs_bits = _check_volume(fn, volume)
+        if vb != B:
+            raise ValueError(f"{fn}: volume of {vb} grids for depths of {B} images")
+        if (volume.color is None) != (images is None):
+            raise ValueError(f"{fn}: images and volume.color go together (both or neither)")
+    _args.max_elems(fn, f"grid={Nz}x{Ny}x{Nx} V={V} source={Hs}x{Ws}", Nx * Ny * Nz, V * 3 * Hs * Ws)
+    _args.one_gpu(fn, dev, transforms, src_masks, src_weights, images, *(() if fresh else (volume.tsdf,)), *_args.prepared_rows(*cameras))
+    with torch.cuda.device(dev):
+        a = dict(B=B, V=V, Hs=Hs, Ws=Ws, Nz=Nz, Ny=Ny, Nx=Nx, vs=vs, vs_bits=vs_bits, trunc=tr, trunc_bits=tr_bits, has_max=has_max,
+                 max_weight=mw, max_weight_bits=mw_bits, dev=dev, fresh=fresh, volume=volume)
+        a["cams"] = [prepare_camera(c, B, dev) for c in cameras]
+        a["src"] = depths.float().contiguous()
+        a["T"] = transforms[..., :3, :].reshape(-1, V, 3, 4).contiguous()
+        a["masks"] = None if src_masks is None else src_masks.contiguous().view(torch.uint8)
+        a["weights"] = None if src_weights is None else src_weights.float().contiguous()
+        a["images"] = None if images is None else images.contiguous()
+        a["origin"] = origin.to(dev).reshape(-1, 3).contiguous() if fresh else volume.origin
+    return a
+
+
+def _result(a, tsdf, weight, color, count, return_count):
+    volume = a["volume"] if not a["fresh"] else TsdfVolume(tsdf, weight, color, a["origin"], a["vs"])
+    return (volume, count) if return_count else volume
+
+
+def _centres(a):
+    """the voxel centres fp32 [B,N,3], x fastest: origin + (index + 0.5) * voxel_size per axis"""
+    dev, B = a["dev"], a["B"]
+    shape = (a["Nz"], a["Ny"], a["Nx"])
+    o = a["origin"]
+    axes = []
+    for k, (n, view) in enumerate(((a["Nx"], (1, 1, 1, -1)), (a["Ny"], (1, 1, -1, 1)), (a["Nz"], (1, -1, 1, 1)))):
+        c = (torch.arange(n, device=dev, dtype=torch.float32) + 0.5) * a["vs"]
+        axes.append((o[:, k].view(-1, 1, 1, 1) + c.view(view)).expand((o.shape[0],) + shape))
+    return torch.stack(axes, dim=-1).reshape(o.shape[0], -1, 3).expand(B, -1, 3).contiguous()
+
+
+def _compose(a, return_count):
+    B, V, dev = a["B"], a["V"], a["dev"]
+    shape = (B, a["Nz"], a["Ny"], a["Nx"])
+    N = a["Nz"] * a["Ny"] * a["Nx"]
+    with_color = a["images"] is not None
+    if a["fresh"]:
+        tsdf, W = torch.ones((B, N), device=dev), torch.zeros((B, N), device=dev)
+        color = torch.zeros((B, 3, N), device=dev) if with_color else None
+    else:
+        vol = a["volume"]
+        tsdf, W = vol.tsdf.reshape(B, N).clone(), vol.weight.reshape(B, N).clone()
+        color = vol.color.reshape(B, 3, N).clone() if with_color else None
+    count = torch.zeros((B, N), device=dev, dtype=torch.uint8)
+    P = _centres(a)
+    # divisors and bounds as device tensors: a division by a host scalar is a multiplication by its reciprocal
+    trunc, one = torch.full((), a["trunc"], device=dev), torch.ones((), device=dev)
+    max_w = torch.full((), a["max_weight"], device=dev)
+    for v in range(V):
+        sd = a["src"][:, v:v + 1]
+        m = sd > 0
+        if a["masks"] is not None:
+            m = m & a["masks"][:, v:v + 1].bool()
+        uv, inside, d = project_camera(P, a["cams"][v], (a["Hs"], a["Ws"]), transform=a["T"][:, v].contiguous())
+        ds, valid = remap(sd, uv, mode="nearest", coord_valid=inside, src_mask=m, return_mask=True)
+        ds = ds[..., 0]
+        wv = one if a["weights"] is None else remap(a["weights"][:, v:v + 1], uv, mode="nearest", coord_valid=inside, src_mask=m)[..., 0]
+        sdf = ds - d
+        obs = valid & (d > 0) & (sdf >= -a["trunc"]) & (wv > 0) & (wv <= _FLT_MAX)
+        s = torch.fmin(sdf / trunc, one)
+        Wn = W + wv
+        tsdf = torch.where(obs, (tsdf * W + s * wv) / Wn, tsdf)
+        if with_color:
+            rgb = remap(a["images"][:, v], uv, mode="nearest", coord_valid=inside, src_mask=m, out_dtype=torch.float32).permute(0, 2, 1)
+            color = torch.where(obs[:, None], (color * W[:, None] + rgb * (wv if wv.ndim == 0 else wv[:, None])) / Wn[:, None], color)
+        W = torch.where(obs, torch.fmin(Wn, max_w) if a["has_max"] else Wn, W)
+        count = count + obs.to(torch.uint8)
+    if not a["fresh"]:
+        vol = a["volume"]
+        vol.tsdf.copy_(tsdf.view(shape))
+        vol.weight.copy_(W.view(shape))
+        if with_color:
+            vol.color.copy_(color.view(B, 3, *shape[1:]))
+    return _result(a, tsdf.view(shape), W.view(shape), color.view(B, 3, *shape[1:]) if with_color else None, count.view(shape), return_count)
+
+
+def tsdf_integrate_composition(volume: Optional[TsdfVolume], depths: torch.Tensor, cameras, transforms: torch.Tensor, *, grid_shape=None,
+                               origin=None, voxel_size: Optional[float] = None, trunc: float, src_masks: Optional[torch.Tensor] = None,
+                               src_weights: Optional[torch.Tensor] = None, images: Optional[torch.Tensor] = None,
+                               max_weight: Optional[float] = None, return_count: bool = False):
+    """tsdf_integrate's definition spelled with the separate calls, in a loop over the views: arguments and results as there.  The voxel
+    centres are built in torch as [B,N,3] rows; per view project_camera(centres, cameras[v], (Hs, Ws), transform=transforms[v]) gives
+    (u, v), inside and the centre's depth; remap(depths[:, v], uv, mode="nearest", coord_valid=inside, src_mask=(depths[:, v] > 0) &
+    src_masks[:, v], return_mask=True) the sampled depth and its validity, and the same remap the weights and the colours; torch
+    element-wise arithmetic, every operation a launch of its own, forms sdf, the decision and the running means.  Three library launches
+    (up to five with weights and colours) and about twenty element-wise ones per view, each a pass over the whole volume.  This is the
+    oracle of the fused kernel's tests and the counterpart of its benchmark."""
+    a = _arguments("tsdf_integrate_composition", volume, depths, cameras, transforms, grid_shape, origin, voxel_size, trunc, src_masks,
+                   src_weights, images, max_weight)
+    with torch.cuda.device(a["dev"]):
+        return _compose(a, return_count)
+
+
+def tsdf_integrate(volume: Optional[TsdfVolume], depths: torch.Tensor, cameras, transforms: torch.Tensor, *, grid_shape=None, origin=None,
+                   voxel_size: Optional[float] = None, trunc: float, src_masks: Optional[torch.Tensor] = None,
+                   src_weights: Optional[torch.Tensor] = None, images: Optional[torch.Tensor] = None, max_weight: Optional[float] = None,
+                   return_count: bool = False):
+    """V depth views of each of B scenes averaged into B truncated signed distance volumes, the whole batch in one launch.
+
+    volume       a TsdfVolume to update IN PLACE (its tensors contiguous fp32 on the GPU, else ValueError), or None: a fresh volume of
+                 grid_shape = (Nz, Ny, Nx) voxels of voxel_size at origin (fp32 [3], [1,3] or [B,3], or three numbers: the grid's corner)
+                 is made by the same single launch, without a memset.
+    depths       [B,V,Hs,Ws] (any float dtype, converted to contiguous fp32), one size for all views.
+    cameras      a sequence of V cameras, one per view, any of the six models.  Cameras are as gtpoints.prepare_camera takes them for B
+                 images; a PreparedCamera is accepted and nothing is copied from the host then (graph capture).
+    transforms   fp32 [V,4,4] or [B,V,4,4] (or the 3x4 forms): volume (world) to view-v-camera coordinates.
+    trunc        the truncation distance, in the volume's units, rounded to fp32; a few voxel sizes.
+    src_masks    bool / uint8 [B,V,Hs,Ws]: view pixels with 0 update nothing.
+    src_weights  [B,V,Hs,Ws] (any float dtype): the weight of each pixel's observation, for example the network's confidence; 1 without.
+                 A pixel whose weight is not a finite positive number updates nothing.
+    images       uint8 [B,V,3,Hs,Ws]: the views' colours, averaged into volume.color with the same weights (a given volume must have
+                 been made with images then, and only then).
+    max_weight   the weight of a voxel is clamped to this after every update (a running mean that keeps adapting); None: no clamp.
+
+    Voxel (ix, iy, iz) of volume b has the centre p = origin + (index + 0.5) * voxel_size per axis.  View v, in view order: q = T p,
+    (u, w) its projection through the view's camera, d its depth (z, or the distance for Spherical); the view's depth ds at the nearest
+    pixel (remap's mode="nearest"), valid as remap's `valid` for coord_valid = the camera's in-image test and src_mask = (depth > 0) &
+    src_masks; sdf = ds - d.  The voxel is updated when valid, d > 0, sdf >= -trunc and the pixel's weight wv is finite and > 0 -- false
+    whenever anything is a NaN: tsdf = (tsdf * W + min(sdf / trunc, 1) * wv) / (W + wv), the colour likewise, W = min(W + wv, max_weight).
+
+    ->  the TsdfVolume (the given one, or the fresh one); with return_count=True (volume, count), count uint8 [B,Nz,Ny,Nx]: the views
+        that updated each voxel in this call.
+
+    One launch, plus the small one that stacks the views' parameter rows.  Stream-ordered, nothing synchronises, no workspace: captures
+    into a graph (with PreparedCamera cameras).  At most 255 views and 256 image-view pairs per call: a longer sequence is integrated by
+    repeated calls on the same volume, which gives the bits of one call over all views.  All six camera models are fused: there is no
+    other path."""
+    fn = "tsdf_integrate"
+    a = _arguments(fn, volume, depths, cameras, transforms, grid_shape, origin, voxel_size, trunc, src_masks, src_weights, images, max_weight)
+    B, V, dev = a["B"], a["V"], a["dev"]
+    shape = (B, a["Nz"], a["Ny"], a["Nx"])
+    with torch.cuda.device(dev):
+        params = torch.stack([c.params for c in a["cams"]])                           # [V,B,16]
+        if a["fresh"]:
+            tsdf = torch.empty(shape, device=dev, dtype=torch.float32)
+            weight = torch.empty(shape, device=dev, dtype=torch.float32)
+            color = torch.empty((B, 3) + shape[1:], device=dev, dtype=torch.float32) if a["images"] is not None else None
+        else:
+            tsdf, weight, color = volume.tsdf, volume.weight, volume.color
+        count = torch.empty(shape, device=dev, dtype=torch.uint8) if return_count else None
+        desc = mk(_lib.UdTsdfIntegrate, src_depth=a["src"], src_mask=a["masks"], src_weight=a["weights"], image=a["images"], params=params,
+                  T=a["T"], origin=a["origin"], tsdf=tsdf, weight=weight, color=color, count=count, B=B, V=V, Nx=a["Nx"], Ny=a["Ny"],
+                  Nz=a["Nz"], Hs=a["Hs"], Ws=a["Ws"], nT=a["T"].shape[0], n_origin=a["origin"].shape[0], fresh=int(a["fresh"]),
+                  has_max_weight=int(a["has_max"]), voxel_size_bits=a["vs_bits"], trunc_bits=a["trunc_bits"],
+                  max_weight_bits=a["max_weight_bits"])
+        for v in range(V):
+            _args.set_models(desc.model, a["cams"][v], v * B)
+        check(_lib.lib.ud_tsdf_integrate(desc, cur_stream()), "ud_tsdf_integrate")
+    return _result(a, tsdf, weight, color, count, return_count)
+
+
+def tsdf_points(volume: TsdfVolume, *, min_weight: float = 1.0, capacity: Optional[int] = None, rgb_dtype: torch.dtype = torch.uint8,
+                workspace: Optional[torch.Tensor] = None) -> PointCloud:
+    """The surface of a TsdfVolume as a packed PointCloud: one point per pair of neighbouring voxels (along +x, +y or +z) whose weights
+    are both >= min_weight and whose distances a, b have different signs ((a < 0) != (b < 0), neither a NaN), at the linear zero crossing:
+    the first voxel's centre moved by t * voxel_size along the axis, t = a / (a - b).  With volume.color the rows carry the colours
+    c0 + t * (c1 - c0) as rgb_dtype: torch.uint8 (rounded half to even, clamped) or torch.float32.
+
+    The order is fixed (volumes in batch order, then voxels x fastest, then the axes x, y, z) and every bit reproducible.
+    capacity = int: outputs are [capacity, 3] and the call makes NO host synchronisation; counts / offsets still hold the true totals, so
+    an overflow is detectable later.  capacity = None: counts first, reads the total back (one synchronisation) and allocates exactly
+    that.  workspace: an optional uint8 GPU tensor of at least ud_tsdf_points_work_bytes(B, Nx, Ny, Nz) bytes to reuse.
+    -> pointcloud.PointCloud (index is None); save_ply(path, cloud.xyz, cloud.rgb) takes it as it is."""
+    fn = "tsdf_points"
+    B, Nz, Ny, Nx, _, vs_bits = _check_volume(fn, volume)
+    try:
+        mw_bits = _args.f32_bits(float(min_weight))
+    except (TypeError, ValueError, OverflowError, struct.error):
+        raise ValueError(f"{fn}: min_weight must be a number in fp32's range") from None
+    if isinstance(min_weight, bool) or math.isnan(float(min_weight)):
+        raise ValueError(f"{fn}: min_weight must be a number, got {min_weight}")
+    if rgb_dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"{fn}: rgb_dtype must be torch.uint8 or torch.float32, got {rgb_dtype}")
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0):
+        raise ValueError(f"{fn}: capacity must be a non-negative int or None")
+    dev = volume.tsdf.device
+    nbytes = int(_lib.lib.ud_tsdf_points_work_bytes(B, Nx, Ny, Nz))
+    if nbytes < 0:
+        raise ValueError(f"{fn}: unsupported sizes B={B} grid={Nz}x{Ny}x{Nx} (3 * Nx * Ny * Nz must stay below 2^31 - 256)")
+    if workspace is None:
+        workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous()
+          or workspace.numel() < nbytes or workspace.data_ptr() % 8):
+        raise ValueError(f"{fn}: workspace must be a contiguous, 8-byte aligned uint8 tensor of at least {nbytes} bytes on {dev}")
+    with_rgb = volume.color is not None
+
+    def run(cap, xyz, rgb):
+        d = mk(_lib.UdTsdfPoints, tsdf=volume.tsdf, weight=volume.weight, color=volume.color, origin=volume.origin, xyz=xyz, rgb=rgb,
+               counts=counts, offsets=offsets, work=workspace, work_bytes=workspace.numel(), capacity=cap, B=B, Nx=Nx, Ny=Ny, Nz=Nz,
+               n_origin=volume.origin.shape[0], rgb_f32=int(rgb_dtype == torch.float32), voxel_size_bits=vs_bits, min_weight_bits=mw_bits)
+        check(_lib.lib.ud_tsdf_points(d, cur_stream()), "ud_tsdf_points")
+
+    with torch.cuda.device(dev):
+        counts = torch.empty(B, device=dev, dtype=torch.int64)
+        offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+        counted = capacity is None
+        if counted:
+            run(0, None, None)                             # count only
+            capacity = int(offsets[B].item())              # the one synchronisation
+        xyz = torch.empty(capacity, 3, device=dev, dtype=torch.float32)
+        rgb = torch.empty(capacity, 3, device=dev, dtype=rgb_dtype) if with_rgb else None
+        if capacity > 0:
+            run(capacity, xyz, rgb)
+        elif not counted:
+            run(0, None, None)
+    return PointCloud(xyz, rgb, None, counts, offsets)
