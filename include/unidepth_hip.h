@@ -839,6 +839,42 @@ typedef struct UdTsdfPoints {
 int ud_tsdf_points(const UdTsdfPoints* desc, void* stream);
 long long ud_tsdf_points_work_bytes(int B, int Nx, int Ny, int Nz);
 
+/* A TSDF volume ray-cast to depth, points, normals and colour in ONE launch (csrc/tsdf_render.hip; the arithmetic of a ray is
+ * csrc/tsdf_ray.h, where the definition is written out operation by operation): one thread per output pixel marches K samples through
+ * the volume, reads the distance trilinearly and stops at the first crossing seen from the front.  No workspace, no atomics, no LDS, no
+ * host synchronisation: captures into a graph.
+ *   Volume b: tsdf, weight fp32 [B,Nz,Ny,Nx] (x fastest), color fp32 planar [B,3,Nz,Ny,Nx] or NULL, origin fp32 [n_origin,3] (n_origin 1
+ *     or B) and voxel_size as UdTsdfIntegrate's.  T fp32 [nT,3,4] (nT = 1 or B) or NULL (identity): CAMERA TO VOLUME coordinates.
+ *   Pixel (py, px) of image b, Ho x Wo: the direction d is the three values of rays (fp32 planar [B,3,Ho,Wo]) as they are, or, with rays
+ *     NULL, ud_camera_unproject's normalised ray of (px + 0.5, py + 0.5) through model[b] / params fp32 [B,16] (closed-form models only:
+ *     Pinhole, EUCM, Spherical, MEI).  With rays the model only selects the depth: the distance for Spherical, z otherwise.
+ *   Sample k = 0 .. K-1: t = near + (float)k * step; p = T (t d); g_a = (p_a - origin_a) / voxel_size - 0.5 per axis.  In the grid when
+ *     0 <= g_a <= N_a - 1 on every axis; then i_a = max(min((int)floorf(g_a), N_a - 2), 0), the upper corner min(i_a + 1, N_a - 1),
+ *     f_a = g_a - i_a.  Valid when in the grid, all eight corner weights >= min_weight and the value s is not a NaN; s is the trilinear
+ *     interpolant a + f * (b - a) along x, then y, then z.
+ *   Scan in order, the previous and the current sample both valid: !(s_prev < 0) && s < 0 is the hit; s_prev < 0 && !(s < 0) ends the
+ *     ray without one (the surface seen from behind).  An invalid sample resets the previous one.
+ *   At the hit: al = s_prev / (s_prev - s); t* = t_(k-1) + al * (t_k - t_(k-1)); points = q* = t* d (camera frame); depth =
+ *     the model's depth of q*; valid = hit && depth > 0, every output of a pixel that is not valid is exactly 0.  normals: the analytic
+ *     gradient of the interpolant at both samples blended with al, rotated by T's rotation transposed, divided by its largest magnitude
+ *     and by its length, turned towards the viewer (n . q* <= 0), exactly 0 where not finite or zero.  color_out: the trilinear colours
+ *     of both samples blended with al, planar [B,3,Ho,Wo], fp32 (color_f32 != 0) or rounded half to even and clamped to a byte.
+ *   Outputs: depth fp32 [B,Ho,Wo] and valid uint8 [B,Ho,Wo] always; points, normals fp32 planar [B,3,Ho,Wo] and color_out optional.
+ *   full_scan != 0: every sample is visited; otherwise the samples that cannot lie in the grid (a conservative ray / box intersection)
+ *     are skipped, which changes no output bit.  wave_patch != 0: a wave renders an 8 x 8 pixel patch instead of 64 pixels of a row; no
+ *     output bit depends on it.  voxel_size_bits / near_bits / step_bits / min_weight_bits hold the bit patterns of the fp32 values.
+ *   Limits: 1 <= B <= UD_RECON_MAX_B; Ho, Wo, Nx, Ny, Nz >= 1; Nx * Ny * Nz and 3 * Ho * Wo < 2^31 - 256; nT (with T) and n_origin 1 or
+ *   B; voxel_size and step finite and > 0; near finite and >= 0; min_weight not a NaN; 1 <= K <= 16384; model tags 1..6, OPENCV and
+ *   Fisheye624 only with rays; params with rays NULL; color_out only with color.  Every refusal is returned before any HIP call.  Built
+ *   with -ffp-contract=off. */
+typedef struct UdTsdfRender {
+  const float* tsdf; const float* weight; const float* color; const float* origin; const float* T; const float* params; const float* rays;
+  float* depth; unsigned char* valid; float* points; float* normals; void* color_out;
+  int B, Ho, Wo, Nx, Ny, Nz, nT, n_origin, K, color_f32, full_scan, wave_patch, voxel_size_bits, near_bits, step_bits, min_weight_bits;
+  unsigned char model[UD_RECON_MAX_B];
+} UdTsdfRender;
+int ud_tsdf_render(const UdTsdfRender* desc, void* stream);
+
 /* Surface normals of a point map, or of a depth map seen through a camera, in ONE launch (csrc/normals.hip; the arithmetic of a pixel is
  * csrc/normals_point.h, where the definition is written out operation by operation).  Exactly one of:
  *     points fp32 planar [B,3,H,W]: the points form.  depth fp32 [B,H,W] is optional there and only feeds the edge test (P.z otherwise).
@@ -1189,7 +1225,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41, UdTsdfIntegrate = 43, UdTsdfPoints = 44; 16, 19, 22, 24, 26, 30, 32, 35, 37, 40 and 42 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41, UdTsdfIntegrate = 43, UdTsdfPoints = 44, UdTsdfRender = 45; 16, 19, 22, 24, 26, 30, 32, 35, 37, 40 and 42 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

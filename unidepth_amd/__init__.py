@@ -18,7 +18,7 @@ _REMAP = ("remap", "undistort", "overlap_mask")
 _WARP = ("warp_camera",)
 _NORMALS = ("normals_from_points", "normals_camera", "eval_normals")
 _CONSISTENCY = ("depth_consistency", "depth_consistency_composition", "invert_rigid")
-_TSDF = ("TsdfVolume", "tsdf_integrate", "tsdf_integrate_composition", "tsdf_points")
+_TSDF = ("TsdfVolume", "tsdf_integrate", "tsdf_integrate_composition", "tsdf_points", "tsdf_render", "tsdf_render_composition")
 __all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP, *_WARP, *_NORMALS,
            *_CONSISTENCY, *_TSDF]
 

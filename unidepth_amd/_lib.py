@@ -174,6 +174,14 @@ class UdTsdfPoints(C.Structure):
                 ("min_weight_bits", i32)]
 
 
+class UdTsdfRender(C.Structure):
+    _fields_ = [("tsdf", vp), ("weight", vp), ("color", vp), ("origin", vp), ("T", vp), ("params", vp), ("rays", vp),
+                ("depth", vp), ("valid", vp), ("points", vp), ("normals", vp), ("color_out", vp),
+                ("B", i32), ("Ho", i32), ("Wo", i32), ("Nx", i32), ("Ny", i32), ("Nz", i32), ("nT", i32), ("n_origin", i32), ("K", i32),
+                ("color_f32", i32), ("full_scan", i32), ("wave_patch", i32), ("voxel_size_bits", i32), ("near_bits", i32), ("step_bits", i32),
+                ("min_weight_bits", i32), ("model", C.c_ubyte * UD_RECON_MAX_B)]
+
+
 UD_EVAL_NORMALS_MAX_T = 8
 
 
@@ -381,6 +389,7 @@ def _load():
         "ud_depth_consistency": [P(UdDepthConsistency), vp],
         "ud_tsdf_integrate": [P(UdTsdfIntegrate), vp],
         "ud_tsdf_points": [P(UdTsdfPoints), vp],
+        "ud_tsdf_render": [P(UdTsdfRender), vp],
         "ud_eval_normals": [P(UdEvalNormals), vp, i64, vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
@@ -416,7 +425,7 @@ def _load():
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency, None, UdTsdfIntegrate, UdTsdfPoints]):
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency, None, UdTsdfIntegrate, UdTsdfPoints, UdTsdfRender]):
         if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35, 37, 40 and 42 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:

@@ -61,6 +61,9 @@ done
 # tsdf: project, the nearest-pixel remap and the running weighted mean fused per voxel over all views (tsdf_point.h calls camera_models.h
 # and remap_taps.h); the volume must have the bits of those launches run one after the other, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c tsdf.hip -o $BD/tsdf.o ) & pids+=($!)
+# tsdf_render: the march, the trilinear reads, the crossing, the gradient and the colour of a ray are defined operation by operation in fp32
+# (tsdf_ray.h under this flag is what the numpy fp32 restatement and the host build of the tests compute), same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c tsdf_render.hip -o $BD/tsdf_render.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)

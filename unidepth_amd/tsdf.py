@@ -5,6 +5,9 @@ depth_consistency when N predicted depth maps, their cameras and their poses bec
     tsdf_integrate(volume, depths, ...)     one ud_tsdf_integrate call (csrc/tsdf.hip): every voxel against every view, any camera model
     tsdf_integrate_composition(...)         the same definition spelled per view with project_camera, remap(mode="nearest") and torch
     tsdf_points(volume, ...)                the zero crossings between neighbouring voxels as a PointCloud (ud_tsdf_points)
+    tsdf_render(volume, camera, size, ...)  the volume ray-cast from a camera: depth, valid, points, normals, colour (ud_tsdf_render,
+                                            csrc/tsdf_render.hip); TsdfVolume.render forwards to it
+    tsdf_render_composition(...)            the same definition spelled in torch, a loop over the samples of the march
 
 For every voxel and every view, in view order: the voxel's centre moved into the view and projected, the view's depth read at the nearest
 pixel, sdf = that depth - the centre's own depth, and where the pixel is valid and the voxel not further than `trunc` behind the surface,
@@ -21,11 +24,13 @@ from typing import Optional, Sequence
 import torch
 
 from . import _args, _lib
+from .consistency import invert_rigid
 from .gtpoints import PreparedCamera, prepare_camera
 from .ops import check, cur_stream, mk
 from .pointcloud import PointCloud
 from .remap import remap
 from .reproject import project_camera
+from .unproject import unproject_camera
 
 _FLT_MAX = 3.4028234663852886e38
 
@@ -37,6 +42,10 @@ class TsdfVolume:
 
     def __init__(self, tsdf: torch.Tensor, weight: torch.Tensor, color: Optional[torch.Tensor], origin: torch.Tensor, voxel_size: float):
         self.tsdf, self.weight, self.color, self.origin, self.voxel_size = tsdf, weight, color, origin, voxel_size
+
+    def render(self, camera, size, transforms=None, **kw):
+        """tsdf_render(self, camera, size, transforms, **kw)"""
+        return tsdf_render(self, camera, size, transforms, **kw)
 
 
 def _positive(fn, name, x):
@@ -333,3 +342,253 @@ def tsdf_points(volume: TsdfVolume, *, min_weight: float = 1.0, capacity: Option
         elif not counted:
             run(0, None, None)
     return PointCloud(xyz, rgb, None, counts, offsets)
+
+
+# ---- the ray cast ------------------------------------------------------------------------------------------------------------------
+
+_MAX_SAMPLES = 16384
+# how ud_tsdf_render runs: a wave renders 64 pixels of a row (or an 8 x 8 pixel patch), and the samples that cannot lie in the grid are
+# skipped (or all are visited).  No output bit depends on either; tools/bench_tsdf_render.py measures all four: rows with the clip is
+# the fastest form at 256^3 (the patch takes 13 - 24 % longer), within 3.3 % of the fastest at 128^3 with B = 1, and up to 17 % slower
+# than the unclipped patch at 128^3 with B = 8 (profiles/tsdf_render_bench.txt).
+_RENDER_OPTIONS = dict(wave_patch=0, full_scan=0)
+
+
+def _number(fn, name, x):
+    """a Python number as (the value of its fp32 rounding, that rounding's bit pattern); not a NaN"""
+    try:
+        bits = _args.f32_bits(float(x))
+    except (TypeError, ValueError, OverflowError, struct.error):
+        raise ValueError(f"{fn}: {name} must be a number in fp32's range") from None
+    val = struct.unpack("<f", struct.pack("<i", bits))[0]
+    if isinstance(x, bool) or math.isnan(val):
+        raise ValueError(f"{fn}: {name} must be a number, got {x}")
+    return val, bits
+
+
+def _render_arguments(fn, volume, camera, size, transforms, rays, near, far, step, min_weight, return_color, color_dtype):
+    """every check both functions share -> the sizes, the scalars and the tensors in the layout of the descriptor"""
+    B, Nz, Ny, Nx, vs, vs_bits = _check_volume(fn, volume)
+    Ho, Wo = _args.image_shape(fn, size, "size")
+    if camera is None:
+        raise ValueError(f"{fn}: camera must be a camera for {B} images (with rays it still selects the depth: distance or z)")
+    _args.batch_of(fn, "camera", _args.n_cameras(camera), B, shared=not isinstance(camera, PreparedCamera))
+    T = None
+    if transforms is not None:
+        shapes = ((4, 4), (3, 4), (1, 4, 4), (1, 3, 4), (B, 4, 4), (B, 3, 4))
+        if not isinstance(transforms, torch.Tensor) or transforms.dtype != torch.float32 or tuple(transforms.shape) not in shapes:
+            raise ValueError(f"{fn}: transforms must be None or fp32 [4,4], [3,4], [{B},4,4] or [{B},3,4]")
+        T = transforms[..., :3, :].reshape(-1, 3, 4)
+    if rays is not None and (not isinstance(rays, torch.Tensor) or rays.dtype != torch.float32 or tuple(rays.shape) != (B, 3, Ho, Wo)):
+        raise ValueError(f"{fn}: rays must be None or fp32 [{B},3,{Ho},{Wo}]")
+    nr, nr_bits = _args.tolerance(fn, "near", near)
+    if isinstance(near, bool):
+        raise ValueError(f"{fn}: near must be a number, got {near}")
+    fr, _ = _number(fn, "far", far)
+    st, st_bits = _positive(fn, "step", vs if step is None else step)
+    mw, mw_bits = _number(fn, "min_weight", min_weight)
+    if not math.isfinite(fr) or fr < nr:
+        raise ValueError(f"{fn}: far must be finite and not below near, got near={near} far={far}")
+    K = int(math.floor((fr - nr) / st)) + 1
+    if K > _MAX_SAMPLES:
+        raise ValueError(f"{fn}: {K} samples between near and far; at most {_MAX_SAMPLES} (a larger step, or a shorter range)")
+    if color_dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"{fn}: color_dtype must be torch.uint8 or torch.float32, got {color_dtype}")
+    if return_color and volume.color is None:
+        raise ValueError(f"{fn}: return_color needs a volume with colours (volume.color is None)")
+    _args.max_elems(fn, f"grid={Nz}x{Ny}x{Nx} size={Ho}x{Wo}", Nx * Ny * Nz, 3 * Ho * Wo)
+    dev = volume.tsdf.device
+    _args.one_gpu(fn, dev, T, rays, *_args.prepared_rows(camera))
+    with torch.cuda.device(dev):
+        cam = prepare_camera(camera, B, dev)
+        if rays is None and _args.n_iterative(cam):                # not fused: the radial loop ends on a maximum over the image
+            rays = unproject_camera(None, cam, normalize=True, image_shape=(Ho, Wo))
+        return dict(B=B, Nz=Nz, Ny=Ny, Nx=Nx, Ho=Ho, Wo=Wo, vs=vs, vs_bits=vs_bits, near=nr, near_bits=nr_bits, step=st, step_bits=st_bits,
+                    min_weight=mw, min_weight_bits=mw_bits, K=K, dev=dev, cam=cam, rays=None if rays is None else rays.contiguous(),
+                    Ti=None if T is None else invert_rigid(T.contiguous()).contiguous())
+
+
+def _render_result(B, Ho, Wo, depth, valid, points, normals, color):
+    res = (depth.view(B, 1, Ho, Wo), valid.view(B, 1, Ho, Wo).view(torch.bool))
+    return res + tuple(x.view(B, 3, Ho, Wo) for x in (points, normals, color) if x is not None)
+
+
+def tsdf_render(volume: TsdfVolume, camera, size, transforms: Optional[torch.Tensor] = None, *, rays: Optional[torch.Tensor] = None,
+                near: float, far: float, step: Optional[float] = None, min_weight: float = 1.0, return_points: bool = False,
+                return_normals: bool = False, return_color: bool = False, color_dtype: torch.dtype = torch.uint8):
+    """A TsdfVolume seen from a camera: every pixel's ray marched through the volume to the first surface it meets from the front, the
+    whole batch in one launch (KinectFusion's surface prediction; dense and occlusion-correct where render_depth's splat leaves holes).
+
+    volume      a TsdfVolume of B grids (contiguous fp32 on the GPU, else ValueError), from tsdf_integrate.
+    camera      as gtpoints.prepare_camera takes it for B images; a PreparedCamera is accepted and nothing is copied from the host then.
+    size        (Ho, Wo) of the rendered images.
+    transforms  fp32 [4,4], [3,4] or [B,4,4] / [B,3,4]: VOLUME (world) TO CAMERA coordinates, tsdf_integrate's convention, so the
+                matrix that integrated a view renders it.  Inverted with consistency.invert_rigid before the launch.  None: identity.
+    rays        fp32 [B,3,Ho,Wo]: the pixels' directions in the camera frame, used as they are in place of the camera's; the camera then
+                only selects the depth (the distance for Spherical, z otherwise).
+    near, far, step   the samples t_k = near + k * step, k = 0 .. K-1, K = floor((far - near) / step) + 1 from the fp32 values; step
+                defaults to volume.voxel_size.  ValueError when far < near or K > 16384.
+    min_weight  a sample counts only where all eight voxels around it have at least this weight.
+
+    Sample k of a pixel with direction d (the camera's normalised ray of the pixel centre): p = T^-1 (t_k d); g = (p - origin) /
+    voxel_size - 0.5 per axis; in the grid when 0 <= g <= N - 1 on every axis; its value s the trilinear interpolant of the eight voxels
+    around it, x then y then z; valid when in the grid, the weights pass and s is not a NaN.  Two valid samples in a row with
+    !(s_prev < 0) and s < 0 are the hit; with s_prev < 0 and !(s < 0) the ray ends without one (the surface seen from behind).  At the hit
+    al = s_prev / (s_prev - s), t* = t_(k-1) + al * (t_k - t_(k-1)), the point q* = t* d and the depth the camera model's depth of q*.
+
+    ->  depth fp32 [B,1,Ho,Wo], valid bool [B,1,Ho,Wo] (hit and depth > 0; every output is exactly 0 where not valid); then, when asked,
+        points   fp32 [B,3,Ho,Wo]: q*, in the camera frame
+        normals  fp32 [B,3,Ho,Wo]: the gradient of the interpolant at both samples blended with al, rotated into the camera frame,
+                 normalised and turned towards the viewer (a fronto-parallel plane gives (0, 0, -1), as normals_from_points); 0 where
+                 it is zero or not finite
+        color    [B,3,Ho,Wo] color_dtype: the trilinear colours of both samples blended with al; torch.uint8 rounds half to even.
+
+    One launch (csrc/tsdf_render.hip; the arithmetic of a ray is csrc/tsdf_ray.h).  With an OPENCV or Fisheye624 member in the camera,
+    whose radial loop ends on a maximum over the whole image, the rays of the batch come from unproject_camera(None, camera,
+    normalize=True, image_shape=size) first, the route warp_camera takes.  Stream-ordered, nothing synchronises, no workspace: captures
+    into a graph (with a PreparedCamera).  The HIP kernel is the only implementation: CPU tensors raise."""
+    fn = "tsdf_render"
+    a = _render_arguments(fn, volume, camera, size, transforms, rays, near, far, step, min_weight, return_color, color_dtype)
+    B, Ho, Wo, dev = a["B"], a["Ho"], a["Wo"], a["dev"]
+    with torch.cuda.device(dev):
+        depth = torch.empty((B, Ho, Wo), device=dev, dtype=torch.float32)
+        valid = torch.empty((B, Ho, Wo), device=dev, dtype=torch.uint8)
+        points = torch.empty((B, 3, Ho, Wo), device=dev, dtype=torch.float32) if return_points else None
+        normals = torch.empty((B, 3, Ho, Wo), device=dev, dtype=torch.float32) if return_normals else None
+        color = torch.empty((B, 3, Ho, Wo), device=dev, dtype=color_dtype) if return_color else None
+        Ti = a["Ti"]
+        desc = mk(_lib.UdTsdfRender, tsdf=volume.tsdf, weight=volume.weight, color=volume.color, origin=volume.origin, T=Ti, params=a["cam"].params,
+                  rays=a["rays"], depth=depth, valid=valid, points=points, normals=normals, color_out=color, B=B, Ho=Ho, Wo=Wo, Nx=a["Nx"],
+                  Ny=a["Ny"], Nz=a["Nz"], nT=0 if Ti is None else Ti.shape[0], n_origin=volume.origin.shape[0], K=a["K"],
+                  color_f32=int(color_dtype == torch.float32), voxel_size_bits=a["vs_bits"], near_bits=a["near_bits"],
+                  step_bits=a["step_bits"], min_weight_bits=a["min_weight_bits"], **_RENDER_OPTIONS)
+        _args.set_models(desc.model, a["cam"])
+        check(_lib.lib.ud_tsdf_render(desc, cur_stream()), "ud_tsdf_render")
+    return _render_result(B, Ho, Wo, depth, valid, points, normals, color)
+
+
+def _sample_t(near, step, k):
+    """t_k = near + (float)k * step with both operations rounded to fp32, as a Python float"""
+    f = lambda x: torch.tensor(x, dtype=torch.float32)             # noqa: E731
+    return float(f(near) + f(float(k)) * f(step))
+
+
+def _lerp(a, b, f):
+    return a + f * (b - a)
+
+
+def _render_compose(a, volume, return_points, return_normals, return_color, color_dtype):
+    B, Ho, Wo, dev = a["B"], a["Ho"], a["Wo"], a["dev"]
+    Nx, Ny, Nz = a["Nx"], a["Ny"], a["Nz"]
+    hw, n = Ho * Wo, Nx * Ny * Nz
+    d = a["rays"] if a["rays"] is not None else unproject_camera(None, a["cam"], normalize=True, image_shape=(Ho, Wo))
+    dx, dy, dz = (c.contiguous() for c in d.reshape(B, 3, hw).unbind(1))
+    T = None if a["Ti"] is None else [a["Ti"][:, r, c].reshape(-1, 1) for r in range(3) for c in range(4)]
+    o = [volume.origin[:, k].reshape(-1, 1) for k in range(3)]
+    vs = torch.full((), a["vs"], device=dev)                       # a divisor as a device tensor: a division, not a reciprocal
+    tsdf, weight = volume.tsdf.reshape(B, n), volume.weight.reshape(B, n)
+    color = volume.color.reshape(B, 3, n) if return_color else None
+    detail = return_normals or return_color
+    mw = a["min_weight"]
+
+    def sample(t):
+        """-> valid, s, the eight distances, (fx, fy, fz), the eight indices"""
+        x, y, z = dx * t, dy * t, dz * t
+        if T is not None:
+            x, y, z = (((T[4 * r] * x + T[4 * r + 1] * y) + T[4 * r + 2] * z) + T[4 * r + 3] for r in range(3))
+        g = [(p - o[k]) / vs - 0.5 for k, p in enumerate((x, y, z))]
+        inside = None
+        for gk, N in zip(g, (Nx, Ny, Nz)):
+            ok = (gk >= 0) & (gk <= float(N - 1))
+            inside = ok if inside is None else inside & ok
+        lo, up, f = [], [], []
+        for gk, N in zip(g, (Nx, Ny, Nz)):
+            gs = torch.where(inside, gk, torch.zeros_like(gk))     # no float becomes an index before it is known to be safe
+            i = torch.floor(gs).long().clamp(max=N - 2).clamp(min=0)
+            lo.append(i)
+            up.append((i + 1).clamp(max=N - 1))
+            f.append(gs - i.float())
+        idx = [((iz * Ny + iy) * Nx + ix) for iz in (lo[2], up[2]) for iy in (lo[1], up[1]) for ix in (lo[0], up[0])]
+        ok = inside
+        for i in idx:
+            ok = ok & (torch.gather(weight, 1, i) >= mw)
+        v = [torch.gather(tsdf, 1, i) for i in idx]
+        s = _tri(v, f)
+        return ok & ~torch.isnan(s), s, v, f, idx
+
+    def _tri(v, f):
+        c00, c10, c01, c11 = _lerp(v[0], v[1], f[0]), _lerp(v[2], v[3], f[0]), _lerp(v[4], v[5], f[0]), _lerp(v[6], v[7], f[0])
+        return _lerp(_lerp(c00, c10, f[1]), _lerp(c01, c11, f[1]), f[2])
+
+    def details(v, f, idx):
+        g = [_lerp(_lerp(v[1] - v[0], v[3] - v[2], f[1]), _lerp(v[5] - v[4], v[7] - v[6], f[1]), f[2]),
+             _lerp(_lerp(v[2] - v[0], v[3] - v[1], f[0]), _lerp(v[6] - v[4], v[7] - v[5], f[0]), f[2]),
+             _lerp(_lerp(v[4] - v[0], v[5] - v[1], f[0]), _lerp(v[6] - v[2], v[7] - v[3], f[0]), f[1])] if return_normals else None
+        c = [_tri([torch.gather(color[:, k], 1, i) for i in idx], f) for k in range(3)] if return_color else None
+        return g, c
+
+    zero = torch.zeros((B, hw), device=dev)
+    false = torch.zeros((B, hw), device=dev, dtype=torch.bool)
+    have, done, hit, sp = false, false, false, zero
+    al, ts = zero, zero
+    G = [zero] * 3 if return_normals else None
+    C = [zero] * 3 if return_color else None
+    prev = None
+    for k in range(a["K"]):
+        t1 = _sample_t(a["near"], a["step"], k)
+        valid, s, v, f, idx = sample(t1)
+        cur = details(v, f, idx) if detail else None
+        both = valid & have & ~done
+        now = both & ~(sp < 0) & (s < 0)
+        if k > 0:
+            t0 = _sample_t(a["near"], a["step"], k - 1)
+            alk = sp / (sp - s)
+            al = torch.where(now, alk, al)
+            ts = torch.where(now, t0 + alk * (t1 - t0), ts)            # t1 - t0: exact in double, rounded to fp32 by the multiply
+            if return_normals:
+                G = [torch.where(now, prev[0][j] + alk * (cur[0][j] - prev[0][j]), G[j]) for j in range(3)]
+            if return_color:
+                C = [torch.where(now, prev[1][j] + alk * (cur[1][j] - prev[1][j]), C[j]) for j in range(3)]
+        hit = hit | now
+        done = done | now | (both & (sp < 0) & ~(s < 0))
+        have, sp, prev = valid, s, cur
+    x, y, z = ts * dx, ts * dy, ts * dz
+    spherical = torch.tensor([m == 3 for m in a["cam"].models], device=dev).reshape(B, 1)
+    dep = torch.where(spherical, torch.sqrt(x * x + y * y + z * z), z)
+    valid = hit & (dep > 0)
+    out = lambda t: torch.where(valid, t, zero)                    # noqa: E731
+    depth = out(dep)
+    points = torch.stack([out(x), out(y), out(z)], dim=1) if return_points else None
+    normals = col = None
+    if return_normals:
+        nx, ny, nz = G
+        if T is not None:
+            nx, ny, nz = ((T[c] * G[0] + T[4 + c] * G[1]) + T[8 + c] * G[2] for c in range(3))
+        finite = torch.isfinite(nx) & torch.isfinite(ny) & torch.isfinite(nz)
+        m = torch.maximum(torch.maximum(nx.abs(), ny.abs()), nz.abs())
+        good = finite & (m > 0)
+        nx, ny, nz = nx / m, ny / m, nz / m
+        length = torch.sqrt((nx * nx + ny * ny) + nz * nz)
+        nx, ny, nz = nx / length, ny / length, nz / length
+        flip = ((nx * x + ny * y) + nz * z) > 0
+        nx, ny, nz = (torch.where(flip, -c, c) for c in (nx, ny, nz))
+        good = good & torch.isfinite(nx) & torch.isfinite(ny) & torch.isfinite(nz) & valid
+        normals = torch.stack([torch.where(good, c, zero) for c in (nx, ny, nz)], dim=1)
+    if return_color:
+        col = torch.stack([out(c) for c in C], dim=1)
+        if color_dtype == torch.uint8:
+            col = torch.where(torch.isnan(col), torch.zeros_like(col), torch.round(col).clamp(0, 255)).to(torch.uint8)
+    return _render_result(B, Ho, Wo, depth, valid.view(torch.uint8), points, normals, col)
+
+
+def tsdf_render_composition(volume: TsdfVolume, camera, size, transforms: Optional[torch.Tensor] = None, *, rays: Optional[torch.Tensor] = None,
+                            near: float, far: float, step: Optional[float] = None, min_weight: float = 1.0, return_points: bool = False,
+                            return_normals: bool = False, return_color: bool = False, color_dtype: torch.dtype = torch.uint8):
+    """tsdf_render's definition spelled in torch: arguments and results as there.  The directions come from unproject_camera(None, camera,
+    normalize=True, image_shape=size) (or `rays`); then a Python loop over the K samples, each a few hundred launches over all pixels:
+    the rigid motion and the grid coordinates element-wise, torch.gather for the eight weights and distances (and colours), torch.where
+    for the scan's state and the crossing.  Every sample of every ray is visited (the full scan).  This is the second oracle of the fused
+    kernel's tests, after the numpy restatement, and the counterpart of its benchmark."""
+    a = _render_arguments("tsdf_render_composition", volume, camera, size, transforms, rays, near, far, step, min_weight, return_color, color_dtype)
+    with torch.cuda.device(a["dev"]):
+        return _render_compose(a, volume, return_points, return_normals, return_color, color_dtype)
