@@ -87,6 +87,29 @@ def case_inputs(name: str):
     raise KeyError(name)
 
 
+MANY_TILES_HW = (518, 518)     # 268,324 samples = 263 tiles of 1024 per image: the scan of an image's tile counts needs its carry
+
+
+def many_tiles_inputs():
+    """A case without a reference golden (so not in CASES): B = 2 at 518 x 518 with about 3,000 valid pixels per image, so the sample
+    grid stays the image (S <= 76,800) and has 263 tiles.  Both images have valid pixels in the tiles 0, 255 (the last of the scan's
+    first chunk of 256), 256 (the second chunk) and 262 (the last, partial tile); tile 1 of image 1 is empty."""
+    H, W = MANY_TILES_HW
+    g = torch.Generator().manual_seed(4263)
+    gts, preds = _points(g, 2, H, W)
+    masks = torch.zeros(2, H * W, dtype=torch.bool)
+    for b in range(2):
+        masks[b, torch.randperm(H * W, generator=g)[:3000]] = True
+        for t in (0, 255, 256, 262):
+            masks[b, t * 1024 + 7 * (b + 1)] = True                    # 262 * 1024 + 14 < 518 * 518
+    masks[0, 1024 + 500] = True
+    masks[1, 1024:2048] = False
+    tiles = np.add.reduceat(masks.numpy().astype(np.int64), np.arange(0, H * W, 1024), axis=1)
+    assert tiles.shape == (2, 263) and (tiles[:, (0, 255, 256, 262)] > 0).all() and tiles[0, 1] > 0 and tiles[1, 1] == 0
+    assert int(masks.sum()) <= 76800 and eval_3d_size(H, W, int(masks.sum())) == (H, W)
+    return gts, preds, masks.view(2, 1, H, W), _thresholds().tolist()
+
+
 def nearest_exact_index(n_in: int, n_out: int) -> np.ndarray:
     """Source index of every output index of F.interpolate(mode="nearest-exact", size=n_out): min(floor((dst + 0.5) * scale), n_in - 1)
     with scale = n_in / n_out and the product in fp32."""

@@ -101,6 +101,14 @@ def test_case_properties():
     assert th == [1.0, 2.0, 4.0] and float((g - g.round()).abs().max()) == 0.0
 
 
+def test_many_tiles_inputs_reach_the_second_chunk_of_the_scan():
+    """the input of test_eval_3d_batch_gpu's 263-tile case (its own assertions: the tiles that hold valid pixels, no resampling)"""
+    from unidepth_amd import eval_ops
+    gts, preds, masks, th = er.many_tiles_inputs()
+    n = masks.flatten(1).sum(1).tolist()
+    assert gts.shape == (2, 3, 518, 518) and all(2900 < k < 3100 for k in n) and eval_ops.eval_3d_size(518, 518, sum(n)) == (518, 518)
+
+
 def test_f1_from_counts():
     assert er.f1_from_counts([5], [5], 10) == 0.0                                            # T = 1: an empty trapezoid
     assert er.f1_from_counts([0, 0], [0, 0], 7) == 0.0                                       # 0 / 0 -> 0

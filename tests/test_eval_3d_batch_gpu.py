@@ -93,6 +93,19 @@ def test_matches_restatement(name):
         np.testing.assert_allclose(got[k], ref[k], rtol=er.RTOL, atol=0, equal_nan=True, err_msg=f"{name}.{k}")
 
 
+def test_matches_restatement_over_more_than_256_tiles():
+    """263 tiles per image: e3_scan_kernel sweeps a second chunk with the carry of the first.  No resampling (518 x 518, about 3,000
+    valid pixels per image), valid pixels in the tiles 0, 255, 256 and the partial last one, an empty tile 1 in one image
+    (eval3d_restate.many_tiles_inputs asserts all that on the host); the assertions of test_matches_restatement"""
+    inputs = er.many_tiles_inputs()
+    got, ref = _run(*inputs), er.restate(*inputs)
+    assert tuple(got["size"]) == ref["size"] == er.MANY_TILES_HW
+    np.testing.assert_array_equal(got["count"], ref["count"])
+    for k in er.KEYS:
+        print("many_tiles", k, got[k], ref[k])
+        np.testing.assert_allclose(got[k], ref[k], rtol=er.RTOL, atol=0, equal_nan=True, err_msg=f"many_tiles.{k}")
+
+
 def test_ties_lattice_reproduces_f1_of_the_integer_counts():
     """squared distances equal to a threshold (1, 2, 4 on an integer lattice) are NOT counted: F1 is bit for bit the value of the
     restatement's integer counts under strict <"""

@@ -15,7 +15,7 @@ _spec = importlib.util.spec_from_file_location("make_golden_pointcloud", os.path
 mg = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(mg)
 
-TILE = 1024          # csrc/pointcloud.hip PC_TILE
+TILE = 1024          # csrc/compact.h CP_TILE
 
 
 def test_golden_has_every_case():
@@ -249,3 +249,10 @@ def test_pack_points_argument_errors():
             pack_points(**kw)
     with pytest.raises(ValueError):
         from_prediction({"depth": dep})
+    # capacity and workspace are judged before anything asks for a GPU, each in its own sentence: a bool is no capacity; the workspace is
+    # a tensor, 8-byte aligned
+    odd = torch.empty(1 << 16, dtype=torch.uint8)[1:]
+    assert odd.data_ptr() % 8
+    for kw, what in ((dict(capacity=True), "capacity"), (dict(workspace=bytearray(1 << 16)), "workspace"), (dict(workspace=odd), "workspace")):
+        with pytest.raises(ValueError, match=f"pack_points: {what} must be"):
+            pack_points(points=pts, **kw)

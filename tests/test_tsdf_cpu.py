@@ -128,6 +128,27 @@ def test_slot_restatement_on_a_planted_volume():
     assert not tc.slots(tsdf, w, None, np.zeros((1, 3), np.float32), 0.5, 1.5)[0].any()
 
 
+def test_many_tiles_volumes_reach_the_second_chunk_of_the_scan():
+    """the input of test_tsdf_gpu's 257-tile case: live slots in the tiles 0, 255 and 256 of both volumes (its own assertions)"""
+    (t, w, c, o), voxel = tc.many_tiles_volumes()
+    assert t.shape == (2, 16, 8, 683) and c.shape == (2, 3, 16, 8, 683) and not np.array_equal(t[0], t[1])
+
+
+def test_points_capacity_and_workspace_errors_without_gpu():
+    """tsdf_points' share of the packing tail it has in common with pack_points (pointcloud._packed): refused in its own sentences
+    before anything is allocated or run (a volume itself must live on the GPU: tests/test_tsdf_gpu.py test_python_surface)"""
+    from unidepth_amd.pointcloud import _packed
+    cpu = torch.device("cpu")
+    odd = torch.empty(1 << 10, dtype=torch.uint8)[1:]
+    assert odd.data_ptr() % 8
+    for kw, what in ((dict(capacity=True), "capacity"), (dict(capacity=-1), "capacity"), (dict(capacity=1.5), "capacity"),
+                     (dict(workspace=bytearray(1 << 10)), "workspace"), (dict(workspace=odd), "workspace"),
+                     (dict(workspace=torch.empty(8, dtype=torch.uint8)), "workspace"), (dict(workspace=torch.empty(1 << 10)), "workspace"),
+                     (dict(workspace=torch.empty(1 << 10, dtype=torch.uint8)[::2]), "workspace")):
+        with pytest.raises(ValueError, match=f"tsdf_points: {what} must be"):
+            _packed("tsdf_points", cpu, 2, 136, None, kw.get("capacity"), kw.get("workspace"), torch.uint8, False)
+
+
 # ---- C-ABI ------------------------------------------------------------------------------------------------------------------------
 
 def _header_fields(name):

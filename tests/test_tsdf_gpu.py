@@ -185,8 +185,10 @@ def test_python_surface():
                 tsdf.TsdfVolume(vol.tsdf[:1], vol.weight[:1], vol.color[:1], vol.origin, vol.voxel_size)):
         with pytest.raises(ValueError, match="tsdf_integrate: "):
             _call(tsdf.tsdf_integrate, d, bad, **ALL)
-    for kw in (dict(min_weight="x"), dict(min_weight=float("nan")), dict(capacity=-1), dict(capacity=1.5), dict(rgb_dtype=torch.float16),
-               dict(workspace=torch.empty(8, dtype=torch.uint8, device="cuda")), dict(workspace=torch.empty(1 << 20, dtype=torch.float32, device="cuda"))):
+    for kw in (dict(min_weight="x"), dict(min_weight=float("nan")), dict(capacity=-1), dict(capacity=1.5), dict(capacity=True),
+               dict(rgb_dtype=torch.float16), dict(workspace=torch.empty(8, dtype=torch.uint8, device="cuda")),
+               dict(workspace=torch.empty(1 << 20, dtype=torch.float32, device="cuda")), dict(workspace=bytearray(1 << 20)),
+               dict(workspace=torch.empty(1 << 20, dtype=torch.uint8, device="cuda")[1:])):
         with pytest.raises(ValueError, match="tsdf_points: "):
             tsdf.tsdf_points(vol, **kw)
 
@@ -227,15 +229,7 @@ def test_special_values(weights):
 def _planted(B, nx, seed, empty=None):
     """a volume of B rows of nx voxels with random distances (a few NaN), weights in {0, 1, 2} and colours; volume `empty` has no weight"""
     from unidepth_amd import tsdf
-    g = np.random.RandomState(9700 + seed)
-    t = g.uniform(-1, 1, size=(B, 1, 1, nx)).astype(np.float32)
-    t[g.uniform(size=t.shape) < 0.03] = np.nan
-    w = g.randint(0, 3, size=t.shape).astype(np.float32)
-    if empty is not None:
-        w[empty] = 0
-    c = g.uniform(0, 255, size=(B, 3, 1, 1, nx)).astype(np.float32)
-    o = g.uniform(-1, 1, size=(B, 3)).astype(np.float32)
-    return tsdf.TsdfVolume(_dev(t), _dev(w), _dev(c), _dev(o), tc.f32(0.05))
+    return tsdf.TsdfVolume(*(_dev(x) for x in tc.planted(B, (1, 1, nx), seed, empty)), tc.f32(0.05))
 
 
 @pytest.mark.parametrize("nx", (341, 342, 683))
@@ -255,6 +249,21 @@ def test_points_around_the_tile(nx):
     assert none.xyz.shape == (0, 3) and none.rgb.shape == (0, 3) and not bool(none.counts.any()) and not bool(none.offsets.any())
     big = tsdf.tsdf_points(vol, capacity=total + 5)                               # rows past the total stay unwritten; the written ones agree
     assert torch.equal(tc.bits(big.xyz[:total]), tc.bits(pc.xyz)) and torch.equal(big.offsets, pc.offsets)
+
+
+def test_points_over_more_than_256_tiles():
+    """257 tiles per volume: the scan of a volume's tile counts takes a second chunk with the carry of the first.  B = 2 different
+    volumes with colours, live slots in the tiles 0, 255 and 256 (asserted on the restatement before the GPU is asked); bit for bit as
+    above, and a capacity below the total"""
+    from unidepth_amd import tsdf
+    arrays, voxel = tc.many_tiles_volumes()
+    vol = tsdf.TsdfVolume(*(_dev(x) for x in arrays), voxel)
+    total = _check_points(vol, "257 tiles")
+    pc = tsdf.tsdf_points(vol)
+    cap = total // 2
+    part = tsdf.tsdf_points(vol, capacity=cap)
+    assert cap > 1024 and torch.equal(part.counts, pc.counts) and torch.equal(part.offsets, pc.offsets) and part.xyz.shape == (cap, 3)
+    assert torch.equal(tc.bits(part.xyz), tc.bits(pc.xyz[:cap])) and torch.equal(part.rgb, pc.rgb[:cap])
 
 
 # ---- guarded C-ABI ------------------------------------------------------------------------------------------------------------------

@@ -199,6 +199,35 @@ def to_u8(x):
     return np.where(r >= 0, np.where(r <= 255, r, 255), 0).astype(np.uint8)
 
 
+def planted(B, grid, seed, empty=None):
+    """B volumes of grid = (Nz, Ny, Nx) voxels with random distances (a few NaN), weights in {0, 1, 2}, colours and origins; volume
+    `empty` has no weight -> tsdf, weight [B,Nz,Ny,Nx], color [B,3,Nz,Ny,Nx], origin [B,3]"""
+    g = np.random.RandomState(9700 + seed)
+    t = g.uniform(-1, 1, size=(B,) + tuple(grid)).astype(np.float32)
+    t[g.uniform(size=t.shape) < 0.03] = np.nan
+    w = g.randint(0, 3, size=t.shape).astype(np.float32)
+    if empty is not None:
+        w[empty] = 0
+    c = g.uniform(0, 255, size=(B, 3) + tuple(grid)).astype(np.float32)
+    o = g.uniform(-1, 1, size=(B, 3)).astype(np.float32)
+    return t, w, c, o
+
+
+MANY_TILES_GRID = (16, 8, 683)     # 87,424 voxels, 262,272 slots = 257 tiles of 1024: the scan of one volume's tile counts needs its carry
+
+
+def many_tiles_volumes():
+    """two different volumes of MANY_TILES_GRID whose restatement has live slots in the tiles 0, 255 (the last of the scan's first
+    chunk of 256), 256 (the second chunk, a partial tile) -> planted()'s arrays and the voxel size"""
+    vol = planted(2, MANY_TILES_GRID, 257)
+    live = slots(vol[0], vol[1], None, vol[3], f32(0.05), 1.0)[0]
+    assert live.shape == (2, 262272)
+    per_tile = np.add.reduceat(live, np.arange(0, live.shape[1], 1024), axis=1)
+    assert per_tile.shape == (2, 257) and (per_tile[:, (0, 255, 256)] > 0).all(), per_tile[:, (0, 255, 256)]
+    assert (per_tile[0] != per_tile[1]).any()
+    return vol, f32(0.05)
+
+
 def packed(live, xyz, rgb):
     """the slot arrays as tsdf_points packs them -> xyz [total,3], rgb [total,3] or None, counts int64 [B], offsets int64 [B+1]"""
     counts = live.sum(axis=1).astype(np.int64)

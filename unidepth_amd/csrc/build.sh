@@ -22,7 +22,7 @@ done
 # 2-D depth metrics: the resample weights, ratios and rescales must round every operation separately (threshold counts), same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c evaldepth.hip -o $BD/evaldepth.o ) & pids+=($!)
 # point-cloud compaction: the filter predicate and the unprojection round every operation separately (a numpy fp32 restatement
-# reproduces the predicate exactly), same rule
+# reproduces the predicate exactly), same rule.  compact.h, which this file, tsdf.hip and eval3d.hip include, is integer code only
 ( hipcc $FLAGS -ffp-contract=off "$@" -c pointcloud.hip -o $BD/pointcloud.o ) & pids+=($!)
 # match_gt: the resample of ud_eval_depth applied to per-image windows; bit-exact against its numpy fp32 restatement, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c matchgt.hip -o $BD/matchgt.o ) & pids+=($!)

@@ -5,10 +5,11 @@
 //   1. e3_count_kernel    valid pixels per 4096-byte slab of the mask -> integer partials
 //   2. e3_size_kernel     S = sum of the partials; the reference's resample size (h, w) in its fp32 arithmetic -> header, `size`
 //   3. e3_flag_kernel     the h x w nearest-exact sample grid of the mask, 1024 samples per tile -> ballot words, tile counts
-//   4. e3_scan_kernel     one workgroup per image: exclusive scan of its tile counts -> tile offsets, counts[b]; zeroes the
-//                         image's threshold counters
-//   5. e3_pack_kernel     valid samples in row-major order -> gt / pred point rows (the order of gt[:, mask]); nearest-neighbour
-//                         slots = +inf; fp64 partial of |gt - pred| per tile
+//                         (csrc/compact.h's cp_flag; steps 3-5 are its ordered compaction)
+//   4. e3_scan_kernel     one workgroup per image: exclusive scan of its tile counts (cp_scan_sweep) -> tile offsets, counts[b];
+//                         zeroes the image's threshold counters
+//   5. e3_pack_kernel     valid samples in row-major order (cp_pack) -> gt / pred point rows (the order of gt[:, mask]);
+//                         nearest-neighbour slots = +inf; fp64 partial of |gt - pred| per tile
 //   6. e3_knn_kernel      d1 = gt -> pred and d2 = pred -> gt, squared L2, K = 1, each direction once, no indices: work items of
 //                         512 queries x 2048 candidates meet in an integer atomicMin on the distance bits (distances are >= 0, so
 //                         the unsigned order is the float order).  The per-pair arithmetic is ud_knn_points' (knn_dist.h).
@@ -20,15 +21,14 @@
 // and surplus workgroups exit on their first test.  Float sums are fp64 partials reduced in a fixed order and the only atomics are
 // integer ones, so the result is bitwise reproducible.  Built with -ffp-contract=off: |gt - pred| and the distances round every
 // multiply and add separately.
-#include "ud_common.h"
+#include "compact.h"
 #include "knn_dist.h"
 
 namespace {
 
-constexpr int E3_THREADS = 256;
-constexpr int E3_STEPS = 4;
-constexpr int E3_TILE = E3_THREADS * E3_STEPS;      // samples per flag / pack tile = points per metric chunk
-constexpr int E3_WORDS = E3_TILE / UD_WAVE;         // 16 ballot words per tile
+constexpr int E3_THREADS = CP_THREADS;              // every kernel of this file runs compact.h's workgroup
+constexpr int E3_STEPS = CP_STEPS;
+constexpr int E3_TILE = CP_TILE;                    // samples per flag / pack tile = points per metric chunk
 constexpr int E3_SLAB = E3_THREADS * 16;            // mask bytes per workgroup of the count
 constexpr int E3_QBLOCK = 2 * E3_THREADS;           // queries per K-NN work item (two per lane)
 constexpr int E3_SPAN = 2 * KNN_TILE;               // candidates per K-NN work item
@@ -55,7 +55,7 @@ E3Layout e3_layout(int B, int H, int W, int T) {
   auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
   L.hdr = 0;
   L.bits = up(sizeof(E3Hdr));
-  L.mse_part = L.bits + tiles * E3_WORDS * sizeof(unsigned long long);
+  L.mse_part = L.bits + tiles * CP_WORDS * sizeof(unsigned long long);
   L.ch_part = L.mse_part + tiles * sizeof(double);
   L.part = L.ch_part + tiles * sizeof(double);
   L.tile_counts = up(L.part + (size_t)L.nP * sizeof(int));
@@ -140,88 +140,38 @@ __device__ __forceinline__ int e3_source(const E3Args& a, const E3Hdr& hd, int p
 }
 
 __global__ __launch_bounds__(E3_THREADS) void e3_flag_kernel(E3Args a) {
-  __shared__ int wave_cnt[E3_THREADS / UD_WAVE];
   const E3Hdr hd = *a.hdr;
-  const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (t >= hd.nTe) return;                          // surplus tile of the H * W bound
-  unsigned long long* words = a.bits + ((size_t)b * a.nT + t) * E3_WORDS;
+  const int t = blockIdx.x, b = blockIdx.y;
+  if (t >= hd.nTe) return;                          // surplus tile of the H * W bound: the whole workgroup leaves
+  const size_t tile = (size_t)b * a.nT + t;
   const unsigned char* mk = a.mask + (size_t)b * a.HW;
-  int cnt = 0;
-#pragma unroll
-  for (int j = 0; j < E3_STEPS; ++j) {
-    const int p = t * E3_TILE + j * E3_THREADS + tid;                 // < hw + E3_TILE <= 2^31 - 1 + 1024: checked on the host
-    const bool v = p < hd.hw && mk[e3_source(a, hd, p)] != 0;
-    const unsigned long long m = __ballot(v);
-    if (lane == 0) words[j * (E3_THREADS / UD_WAVE) + w] = m;
-    cnt += __popcll(m);
-  }
-  if (lane == 0) wave_cnt[w] = cnt;
-  __syncthreads();
-  if (tid == 0) a.tile_counts[(size_t)b * a.nT + t] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+  // a sample index is < hw + E3_TILE <= 2^31 - 1 + 1024: checked on the host
+  cp_flag(a.bits + tile * CP_WORDS, a.tile_counts + tile, t, hd.hw, [=](int p) { return mk[e3_source(a, hd, p)] != 0; });
 }
 
-// One workgroup per image: exclusive scan of its nTe tile counts, swept in chunks of E3_THREADS with a running carry.
+// One workgroup per image: exclusive scan of its nTe tile counts (int sums: an image has fewer than 2^31 samples).
 __global__ __launch_bounds__(E3_THREADS) void e3_scan_kernel(E3Args a) {
-  __shared__ int wave_tot[E3_THREADS / UD_WAVE];
   const E3Hdr hd = *a.hdr;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int* in = a.tile_counts + (size_t)b * a.nT;
-  int* out = a.tile_offs + (size_t)b * a.nT;
+  const int b = blockIdx.x, tid = threadIdx.x;
   for (int t = tid; t < 2 * a.T; t += E3_THREADS) a.thr_cnt[(size_t)b * 2 * a.T + t] = 0u;
-  int carry = 0;
-  for (int base = 0; base < hd.nTe; base += E3_THREADS) {
-    const int i = base + tid;
-    const int v = i < hd.nTe ? in[i] : 0;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < UD_WAVE; o <<= 1) {
-      const int up = __shfl_up(inc, o, UD_WAVE);
-      if (lane >= o) inc += up;
-    }
-    if (lane == UD_WAVE - 1) wave_tot[w] = inc;
-    __syncthreads();
-    int before = 0, chunk = 0;
-#pragma unroll
-    for (int k = 0; k < E3_THREADS / UD_WAVE; ++k) {
-      const int tk = wave_tot[k];
-      if (k < w) before += tk;
-      chunk += tk;
-    }
-    if (i < hd.nTe) out[i] = carry + before + inc - v;
-    carry += chunk;
-    __syncthreads();                                // wave_tot is rewritten by the next chunk
-  }
-  if (tid == 0) a.counts[b] = carry;
+  const int total = cp_scan_sweep<int>(a.tile_counts + (size_t)b * a.nT, a.tile_offs + (size_t)b * a.nT, hd.nTe);
+  if (tid == 0) a.counts[b] = total;
 }
 
 __global__ __launch_bounds__(E3_THREADS) void e3_pack_kernel(E3Args a) {
   __shared__ double wave_tot[E3_THREADS / UD_WAVE];
   const E3Hdr hd = *a.hdr;
-  const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int t = blockIdx.x, b = blockIdx.y;
   if (t >= hd.nTe) return;
-  const int base = a.tile_offs[(size_t)b * a.nT + t];
-  // lanes 0..15 of every wave hold the tile's 16 words and the count of valid samples in the words before each
-  const unsigned long long my_word = lane < E3_WORDS ? a.bits[((size_t)b * a.nT + t) * E3_WORDS + lane] : 0ull;
-  const int my_cnt = __popcll(my_word);
-  int inc = my_cnt;
-#pragma unroll
-  for (int o = 1; o < E3_WORDS; o <<= 1) {
-    const int up = __shfl_up(inc, o, UD_WAVE);
-    if (lane >= o) inc += up;
-  }
-  const int my_before = inc - my_cnt;
+  const size_t tile = (size_t)b * a.nT + t;
+  const int base = a.tile_offs[tile];
   const float* G = a.gt + (size_t)b * 3 * a.HW;
   const float* P = a.pred + (size_t)b * 3 * a.HW;
   const size_t HW = (size_t)a.HW, BHW = (size_t)a.B * HW;
   double acc = 0.0;
-#pragma unroll
-  for (int j = 0; j < E3_STEPS; ++j) {
-    const int k = j * (E3_THREADS / UD_WAVE) + w;
-    const unsigned long long m = __shfl(my_word, k, UD_WAVE);
-    const int before = __shfl(my_before, k, UD_WAVE);
-    if (!((m >> lane) & 1ull)) continue;
-    const size_t r = (size_t)b * HW + (size_t)(base + before + __popcll(m & ((1ull << lane) - 1ull)));   // row < (b + 1) * HW
-    const int src = e3_source(a, hd, t * E3_TILE + k * UD_WAVE + lane);                                  // a set bit: sample < hw
+  cp_pack(a.bits + tile * CP_WORDS, t, [=, &acc](int p, int row) {
+    const size_t r = (size_t)b * HW + (size_t)(base + row);         // row < (b + 1) * HW
+    const int src = e3_source(a, hd, p);
     const float gx = G[src], gy = G[HW + src], gz = G[2 * HW + src];
     const float px = P[src], py = P[HW + src], pz = P[2 * HW + src];
     float* og = a.gt_xyz + r * 3;
@@ -232,9 +182,9 @@ __global__ __launch_bounds__(E3_THREADS) void e3_pack_kernel(E3Args a) {
     a.dmin[BHW + r] = E3_INF_BITS;
     const float dx = gx - px, dy = gy - py, dz = gz - pz;
     acc += (double)sqrtf((dx * dx + dy * dy) + dz * dz);
-  }
-  const double tot = e3_block_sum(acc, wave_tot);
-  if (tid == 0) a.mse_part[(size_t)b * a.nT + t] = tot;
+  });
+  const double tot = e3_block_sum(acc, wave_tot);   // after the helper: every thread reaches its barriers
+  if (threadIdx.x == 0) a.mse_part[tile] = tot;
 }
 
 // blockIdx.y = direction * B + image; the workgroups of one (direction, image) stride over its work items (512 queries x 2048

@@ -7,15 +7,16 @@
 //                           costs one projection and one nearest-pixel gather (and its mask's, weight's and colour's).  All six camera
 //                           models: projection is closed form for every one of them.  No LDS, no atomics, no workspace, no host
 //                           synchronisation: captures into a graph.
-//   tp_* kernels            the ordered compaction of pointcloud.hip over slots (3 * voxel + axis) instead of pixels: tiles of 1024
-//                           consecutive slots of one volume, ballot words, a scan per volume, a scan over the volumes, a pack.  Every
-//                           dependency is a launch boundary: no atomics, no spinning; the order (volumes, then slots) and the bits are fixed.
+//   tp_* kernels            the ordered compaction of csrc/compact.h over slots (3 * voxel + axis): tp_flag_kernel (cp_flag over
+//                           ud_tsdf_slot), compact.h's scan per volume and scan over the volumes, tp_pack_kernel (cp_pack, the slot's row).
+//                           Every dependency is a launch boundary: no atomics, no spinning; the order (volumes, then slots) and the bits
+//                           are fixed.
 //
 // The arithmetic of a voxel and of a slot is csrc/tsdf_point.h, which only calls csrc/camera_models.h and csrc/remap_taps.h; the host build
 // of the tests runs it under the sanitizers.  Built with -ffp-contract=off: every operation rounds separately, so the volume has the bits
 // of project_camera, remap and the element-wise arithmetic run one after the other.
 #include <math.h>
-#include "ud_common.h"
+#include "compact.h"
 #include "tsdf_point.h"
 #pragma clang fp contract(off)
 
@@ -34,120 +35,29 @@ __global__ __launch_bounds__(TS_THREADS) void ts_integrate_kernel(const TsKernel
   ud_tsdf_voxel(a.p, a.model, (int)blockIdx.y, i);
 }
 
-// ---- surface extraction: pointcloud.hip's flag / scan / pack over slots ---------------------------------------------------------------
-constexpr int TP_THREADS = 256;
-constexpr int TP_STEPS = 4;
-constexpr int TP_TILE = TP_THREADS * TP_STEPS;
-constexpr int TP_WORDS = TP_TILE / UD_WAVE;            // 16 ballot words per tile
-constexpr int TP_SCAN = 256;
-
-struct TpLayout {
-  size_t bits, tile_counts, tile_offs, total;
-  int nT;
-};
-
-TpLayout tp_layout(int B, long long slots) {
-  TpLayout L;
-  L.nT = (int)((slots + TP_TILE - 1) / TP_TILE);
-  const size_t tiles = (size_t)B * L.nT;
-  L.bits = 0;
-  L.tile_counts = tiles * TP_WORDS * sizeof(unsigned long long);
-  L.tile_offs = L.tile_counts + tiles * sizeof(int);
-  L.total = L.tile_offs + tiles * sizeof(int);
-  return L;
-}
-
+// ---- surface extraction: compact.h's flag / scan / pack over slots -------------------------------------------------------------------
 struct TpArgs {
   UdTsdfSlotArgs p;
-  float* xyz; void* rgb; long long* counts; long long* offsets;
-  unsigned long long* bits; int* tile_counts; int* tile_offs;
+  float* xyz; void* rgb;
+  CpArgs c;
   long long capacity;
-  int slots, nT, rgb_f32;
+  int slots, rgb_f32;
 };
 
-__global__ __launch_bounds__(TP_THREADS) void tp_flag_kernel(TpArgs a) {
-  __shared__ int wave_cnt[TP_THREADS / UD_WAVE];
-  const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  unsigned long long* words = a.bits + ((size_t)b * a.nT + t) * TP_WORDS;
-  int cnt = 0;
-#pragma unroll
-  for (int j = 0; j < TP_STEPS; ++j) {
-    const unsigned s = (unsigned)t * TP_TILE + j * TP_THREADS + tid;       // < 2^31 + TP_TILE: fits unsigned
-    const bool v = s < (unsigned)a.slots && ud_tsdf_slot(a.p, b, (long long)s, nullptr, nullptr);
-    const unsigned long long m = __ballot(v);                              // tails are false: every lane reaches every ballot
-    if (lane == 0) words[j * (TP_THREADS / UD_WAVE) + w] = m;
-    cnt += __popcll(m);
-  }
-  if (lane == 0) wave_cnt[w] = cnt;
-  __syncthreads();
-  if (tid == 0) a.tile_counts[(size_t)b * a.nT + t] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+__global__ __launch_bounds__(CP_THREADS) void tp_flag_kernel(TpArgs a) {
+  const int t = blockIdx.x, b = blockIdx.y;
+  const size_t tile = (size_t)b * a.c.nT + t;
+  cp_flag(a.c.bits + tile * CP_WORDS, a.c.tile_counts + tile, t, a.slots,
+          [=](unsigned s) { return ud_tsdf_slot(a.p, b, (long long)s, nullptr, nullptr); });
 }
 
-// Exclusive scan of in[0..n) by one workgroup of TP_SCAN threads, swept in chunks of TP_SCAN with a running carry; returns the total (the
-// same value in every thread).  Integer sums: the order does not matter for the bits.  (pointcloud.hip's sweep, which is local to that file.)
-template <class TI, class TO>
-__device__ long long tp_scan_sweep(const TI* in, TO* out, int n) {
-  __shared__ long long wave_tot[TP_SCAN / UD_WAVE];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  long long carry = 0;
-  for (int base = 0; base < n; base += TP_SCAN) {
-    const int i = base + tid;
-    const long long v = i < n ? (long long)in[i] : 0;
-    long long inc = v;
-#pragma unroll
-    for (int o = 1; o < UD_WAVE; o <<= 1) {
-      const long long up = __shfl_up(inc, o, UD_WAVE);
-      if (lane >= o) inc += up;
-    }
-    if (lane == UD_WAVE - 1) wave_tot[w] = inc;
-    __syncthreads();
-    long long before = 0, chunk = 0;
-#pragma unroll
-    for (int k = 0; k < TP_SCAN / UD_WAVE; ++k) {
-      const long long tk = wave_tot[k];
-      if (k < w) before += tk;
-      chunk += tk;
-    }
-    if (i < n) out[i] = (TO)(carry + before + inc - v);
-    carry += chunk;
-    __syncthreads();                                   // wave_tot is rewritten by the next chunk
-  }
-  return carry;
-}
-
-__global__ __launch_bounds__(TP_SCAN) void tp_scan_tiles_kernel(TpArgs a) {
-  const int b = blockIdx.x;
-  const long long total = tp_scan_sweep(a.tile_counts + (size_t)b * a.nT, a.tile_offs + (size_t)b * a.nT, a.nT);
-  if (threadIdx.x == 0) a.counts[b] = total;
-}
-
-__global__ __launch_bounds__(TP_SCAN) void tp_scan_volumes_kernel(TpArgs a) {
-  const long long total = tp_scan_sweep(a.counts, a.offsets, a.p.B);
-  if (threadIdx.x == 0) a.offsets[a.p.B] = total;
-}
-
-__global__ __launch_bounds__(TP_THREADS) void tp_pack_kernel(TpArgs a) {
-  const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const long long base = a.offsets[b] + a.tile_offs[(size_t)b * a.nT + t];
-  // lanes 0..15 of every wave hold the tile's 16 words and the count of live slots in the words before each
-  const unsigned long long my_word = lane < TP_WORDS ? a.bits[((size_t)b * a.nT + t) * TP_WORDS + lane] : 0ull;
-  const int my_cnt = __popcll(my_word);
-  int inc = my_cnt;
-#pragma unroll
-  for (int o = 1; o < TP_WORDS; o <<= 1) {
-    const int up = __shfl_up(inc, o, UD_WAVE);
-    if (lane >= o) inc += up;
-  }
-  const int my_before = inc - my_cnt;
-#pragma unroll
-  for (int j = 0; j < TP_STEPS; ++j) {
-    const int k = j * (TP_THREADS / UD_WAVE) + w;
-    const unsigned long long m = __shfl(my_word, k, UD_WAVE);
-    const int before = __shfl(my_before, k, UD_WAVE);
-    if (!((m >> lane) & 1ull)) continue;
-    const long long r = base + before + __popcll(m & ((1ull << lane) - 1ull));
-    if (r >= a.capacity) continue;
-    const long long s = (long long)t * TP_TILE + k * UD_WAVE + lane;        // a set bit: s < slots
+__global__ __launch_bounds__(CP_THREADS) void tp_pack_kernel(TpArgs a) {
+  const int t = blockIdx.x, b = blockIdx.y;
+  const size_t tile = (size_t)b * a.c.nT + t;
+  const long long base = a.c.offsets[b] + a.c.tile_offs[tile];
+  cp_pack(a.c.bits + tile * CP_WORDS, t, [=](int s, int row) {
+    const long long r = base + row;
+    if (r >= a.capacity) return;
     float xyz[3], rgb[3] = {0.0f, 0.0f, 0.0f};
     ud_tsdf_slot(a.p, b, s, xyz, rgb);
     float* o = a.xyz + r * 3;
@@ -161,7 +71,7 @@ __global__ __launch_bounds__(TP_THREADS) void tp_pack_kernel(TpArgs a) {
         oc[0] = ud_rm_to_u8(rgb[0]); oc[1] = ud_rm_to_u8(rgb[1]); oc[2] = ud_rm_to_u8(rgb[2]);
       }
     }
-  }
+  });
 }
 
 bool ts_positive(float x) { return x > 0.0f && x <= 3.402823466e38f; }     // finite and > 0 (false for a NaN)
@@ -239,7 +149,7 @@ static long long tp_slots(int B, int Nx, int Ny, int Nz) {
 
 extern "C" long long ud_tsdf_points_work_bytes(int B, int Nx, int Ny, int Nz) {
   const long long slots = tp_slots(B, Nx, Ny, Nz);
-  return slots < 0 ? -1 : (long long)tp_layout(B, slots).total;
+  return slots < 0 ? -1 : (long long)cp_layout(B, slots).total;
 }
 
 extern "C" int ud_tsdf_points(const UdTsdfPoints* desc, void* stream) {
@@ -274,27 +184,25 @@ extern "C" int ud_tsdf_points(const UdTsdfPoints* desc, void* stream) {
     ud_set_error("ud_tsdf_points: min_weight must not be a NaN");
     return UD_ERR_BAD_ARG;
   }
-  const TpLayout L = tp_layout(d.B, slots);
+  const CpLayout L = cp_layout(d.B, slots);
   if (d.work_bytes < (long long)L.total) {
     ud_set_error("ud_tsdf_points: workspace smaller than ud_tsdf_points_work_bytes()");
     return UD_ERR_BAD_ARG;
   }
-  char* w = (char*)d.work;
   TpArgs a;
   a.p.tsdf = d.tsdf; a.p.weight = d.weight; a.p.color = d.color; a.p.origin = d.origin;
   a.p.n = slots / 3;
   a.p.vs = vs; a.p.min_weight = min_weight;
   a.p.B = d.B; a.p.Nx = d.Nx; a.p.Ny = d.Ny; a.p.Nz = d.Nz; a.p.nO = d.n_origin;
-  a.xyz = d.xyz; a.rgb = d.rgb; a.counts = d.counts; a.offsets = d.offsets;
-  a.bits = (unsigned long long*)(w + L.bits); a.tile_counts = (int*)(w + L.tile_counts); a.tile_offs = (int*)(w + L.tile_offs);
+  a.xyz = d.xyz; a.rgb = d.rgb;
+  a.c = cp_args(L, d.work, d.counts, d.offsets, d.B);
   a.capacity = d.capacity;
-  a.slots = (int)slots; a.nT = L.nT; a.rgb_f32 = d.rgb_f32 != 0;
+  a.slots = (int)slots; a.rgb_f32 = d.rgb_f32 != 0;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)L.nT, (unsigned)d.B);
-  hipLaunchKernelGGL(tp_flag_kernel, grid, dim3(TP_THREADS), 0, s, a);
-  hipLaunchKernelGGL(tp_scan_tiles_kernel, dim3((unsigned)d.B), dim3(TP_SCAN), 0, s, a);
-  hipLaunchKernelGGL(tp_scan_volumes_kernel, dim3(1), dim3(TP_SCAN), 0, s, a);
-  if (d.xyz && d.capacity > 0) hipLaunchKernelGGL(tp_pack_kernel, grid, dim3(TP_THREADS), 0, s, a);
+  hipLaunchKernelGGL(tp_flag_kernel, grid, dim3(CP_THREADS), 0, s, a);
+  cp_launch_scans(a.c, s);
+  if (d.xyz && d.capacity > 0) hipLaunchKernelGGL(tp_pack_kernel, grid, dim3(CP_THREADS), 0, s, a);
   UD_CHECK_LAUNCH("ud_tsdf_points launch");
   return UD_OK;
 }

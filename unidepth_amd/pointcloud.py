@@ -66,7 +66,8 @@ def pack_points(points: Optional[torch.Tensor] = None, *, depth: Optional[torch.
 
     capacity = int: outputs are [capacity, 3] and the call makes NO host synchronisation; counts / offsets still hold the true totals,
     so an overflow is detectable later.  capacity = None: counts first, reads the total back (one synchronisation) and allocates
-    exactly that.  workspace: an optional uint8 GPU tensor of at least ud_pointcloud_work_bytes(B, H, W) bytes to reuse."""
+    exactly that.  workspace: an optional contiguous, 8-byte aligned uint8 GPU tensor of at least ud_pointcloud_work_bytes(B, H, W)
+    bytes to reuse."""
     if points is None and depth is None:
         raise ValueError("pack_points: points or depth is required")
     lead = points if points is not None else depth
@@ -118,39 +119,50 @@ def pack_points(points: Optional[torch.Tensor] = None, *, depth: Optional[torch.
     if edge_rtol is not None:
         flags |= _lib.UD_PC_EDGE
         rtol = float(edge_rtol)
-    if capacity is not None and (not isinstance(capacity, int) or capacity < 0):
-        raise ValueError("pack_points: capacity must be a non-negative int or None")
-    dev = lead.device
-    for name, t in tensors.items():
-        if not t.is_cuda or t.device != dev:
-            raise ValueError(f"pack_points: {name} must live on the GPU of the first input ({dev}); there is no CPU path")
     nbytes = int(_lib.lib.ud_pointcloud_work_bytes(B, H, W))
     if nbytes < 0 or (return_index and B * H * W > 2 ** 31 - 1):
         raise ValueError(f"pack_points: unsupported sizes B={B} H={H} W={W}")
-    if workspace is None:
-        workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < nbytes:
-        raise ValueError(f"pack_points: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes on {dev}")
-    counts = torch.empty(B, device=dev, dtype=torch.int64)
-    offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
 
-    def run(cap, xyz, rgb, index):
-        d = mk(_lib.UdPointCloud, xyz=xyz, rgb=rgb, index=index, counts=counts, offsets=offsets, work=workspace, work_bytes=workspace.numel(),
-               capacity=cap, B=B, H=H, W=W, nK=nK, flags=flags, min_conf=min_conf, dmin=dmin, dmax=dmax, edge_rtol=rtol, **tensors)
+    def run(cap, xyz, rgb, index, **work):
+        d = mk(_lib.UdPointCloud, xyz=xyz, rgb=rgb, index=index, capacity=cap, B=B, H=H, W=W, nK=nK, flags=flags, min_conf=min_conf, dmin=dmin,
+               dmax=dmax, edge_rtol=rtol, **tensors, **work)
         check(_lib.lib.ud_pointcloud_pack(d, cur_stream()), "ud_pointcloud_pack")
 
+    return _packed("pack_points", lead.device, B, nbytes, run, capacity, workspace, None if image is None else image.dtype, return_index,
+                   inputs=tensors)
+
+
+def _packed(fn, dev, B, nbytes, run, capacity, workspace, rgb_dtype, want_index, inputs=None) -> PointCloud:
+    """The tail every packer over csrc/compact.h shares (pack_points, tsdf.tsdf_points): the checks of `capacity` and `workspace` (nbytes:
+    what the packer's *_work_bytes() asks for) in fn's own sentences, counts / offsets, and run(cap, xyz, rgb, index, **work) -- the
+    packer's one C call, `work` being the descriptor's counts, offsets, work and work_bytes -- once with the given capacity (no host
+    synchronisation), or count-only, one read-back, then exactly the total.  rgb_dtype None: no rgb rows; inputs: named tensors that must
+    live on dev."""
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0):
+        raise ValueError(f"{fn}: capacity must be a non-negative int or None")
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev
+                                  or not workspace.is_contiguous() or workspace.numel() < nbytes or workspace.data_ptr() % 8):
+        raise ValueError(f"{fn}: workspace must be a contiguous, 8-byte aligned uint8 tensor of at least {nbytes} bytes on {dev}")
+    for name, t in (inputs or {}).items():
+        if not t.is_cuda or t.device != dev:
+            raise ValueError(f"{fn}: {name} must live on the GPU of the first input ({dev}); there is no CPU path")
     with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        counts = torch.empty(B, device=dev, dtype=torch.int64)
+        offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+        work = dict(counts=counts, offsets=offsets, work=workspace, work_bytes=workspace.numel())
         counted = capacity is None
         if counted:
-            run(0, None, None, None)                       # count only
+            run(0, None, None, None, **work)               # count only
             capacity = int(offsets[B].item())              # the one synchronisation
         xyz = torch.empty(capacity, 3, device=dev, dtype=torch.float32)
-        rgb = torch.empty(capacity, 3, device=dev, dtype=image.dtype) if image is not None else None
-        index = torch.empty(capacity, device=dev, dtype=torch.int32) if return_index else None
+        rgb = torch.empty(capacity, 3, device=dev, dtype=rgb_dtype) if rgb_dtype is not None else None
+        index = torch.empty(capacity, device=dev, dtype=torch.int32) if want_index else None
         if capacity > 0:
-            run(capacity, xyz, rgb, index)
+            run(capacity, xyz, rgb, index, **work)
         elif not counted:
-            run(0, None, None, None)
+            run(0, None, None, None, **work)
     return PointCloud(xyz, rgb, index, counts, offsets)
 
 

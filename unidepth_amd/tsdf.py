@@ -27,7 +27,7 @@ from . import _args, _lib
 from .consistency import invert_rigid
 from .gtpoints import PreparedCamera, prepare_camera
 from .ops import check, cur_stream, mk
-from .pointcloud import PointCloud
+from .pointcloud import PointCloud, _packed
 from .remap import remap
 from .reproject import project_camera
 from .unproject import unproject_camera
@@ -309,39 +309,17 @@ def tsdf_points(volume: TsdfVolume, *, min_weight: float = 1.0, capacity: Option
         raise ValueError(f"{fn}: min_weight must be a number, got {min_weight}")
     if rgb_dtype not in (torch.uint8, torch.float32):
         raise ValueError(f"{fn}: rgb_dtype must be torch.uint8 or torch.float32, got {rgb_dtype}")
-    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0):
-        raise ValueError(f"{fn}: capacity must be a non-negative int or None")
-    dev = volume.tsdf.device
     nbytes = int(_lib.lib.ud_tsdf_points_work_bytes(B, Nx, Ny, Nz))
     if nbytes < 0:
         raise ValueError(f"{fn}: unsupported sizes B={B} grid={Nz}x{Ny}x{Nx} (3 * Nx * Ny * Nz must stay below 2^31 - 256)")
-    if workspace is None:
-        workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous()
-          or workspace.numel() < nbytes or workspace.data_ptr() % 8):
-        raise ValueError(f"{fn}: workspace must be a contiguous, 8-byte aligned uint8 tensor of at least {nbytes} bytes on {dev}")
-    with_rgb = volume.color is not None
 
-    def run(cap, xyz, rgb):
+    def run(cap, xyz, rgb, index, **work):
         d = mk(_lib.UdTsdfPoints, tsdf=volume.tsdf, weight=volume.weight, color=volume.color, origin=volume.origin, xyz=xyz, rgb=rgb,
-               counts=counts, offsets=offsets, work=workspace, work_bytes=workspace.numel(), capacity=cap, B=B, Nx=Nx, Ny=Ny, Nz=Nz,
-               n_origin=volume.origin.shape[0], rgb_f32=int(rgb_dtype == torch.float32), voxel_size_bits=vs_bits, min_weight_bits=mw_bits)
+               capacity=cap, B=B, Nx=Nx, Ny=Ny, Nz=Nz, n_origin=volume.origin.shape[0], rgb_f32=int(rgb_dtype == torch.float32),
+               voxel_size_bits=vs_bits, min_weight_bits=mw_bits, **work)
         check(_lib.lib.ud_tsdf_points(d, cur_stream()), "ud_tsdf_points")
 
-    with torch.cuda.device(dev):
-        counts = torch.empty(B, device=dev, dtype=torch.int64)
-        offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
-        counted = capacity is None
-        if counted:
-            run(0, None, None)                             # count only
-            capacity = int(offsets[B].item())              # the one synchronisation
-        xyz = torch.empty(capacity, 3, device=dev, dtype=torch.float32)
-        rgb = torch.empty(capacity, 3, device=dev, dtype=rgb_dtype) if with_rgb else None
-        if capacity > 0:
-            run(capacity, xyz, rgb)
-        elif not counted:
-            run(0, None, None)
-    return PointCloud(xyz, rgb, None, counts, offsets)
+    return _packed(fn, volume.tsdf.device, B, nbytes, run, capacity, workspace, None if volume.color is None else rgb_dtype, False)
 
 
 # ---- the ray cast ------------------------------------------------------------------------------------------------------------------
