@@ -839,6 +839,43 @@ typedef struct UdTsdfPoints {
 int ud_tsdf_points(const UdTsdfPoints* desc, void* stream);
 long long ud_tsdf_points_work_bytes(int B, int Nx, int Ny, int Nz);
 
+/* The surface of a TSDF volume as an indexed triangle mesh (csrc/tsdf_mesh.hip; the arithmetic of a cell and of a quad is
+ * csrc/tsdf_mesh_point.h): naive surface nets as two of UdTsdfPoints' ordered compactions, one over cells and one over slots; no case
+ * table, no atomics, no host synchronisation.  The volume, min_weight, the voxel centres, the slots and a slot's crossing point and
+ * colour are UdTsdfPoints'.  Every operation rounded separately in fp32.
+ *   Cells.  The cell of voxel i = (iz * Ny + iy) * Nx + ix has the corners (ix + dx, iy + dy, iz + dz), d* in {0, 1}; it exists when
+ *     ix + 1 < Nx, iy + 1 < Ny and iz + 1 < Nz.  It is live when all eight weights are >= min_weight, no corner distance is a NaN and the
+ *     corners are not all of one sign (d < 0 is the sign).  A grid with an axis of one voxel has no cells: an empty mesh.
+ *   Vertices: one per live cell; volumes in batch order, then cells in voxel order.  The cell's edges e = 4 * axis + k, k = 0..3: with
+ *     (o0, o1) the two other axes ascending, the edge's lower voxel is the cell's voxel moved by k & 1 along o0 and (k >> 1) & 1 along o1,
+ *     and the edge is slot 3 * lower + axis.  The vertex is the sum of the live slots' crossing points in edge order (the first one
+ *     initialises the sum) divided by (float)their number; rgb the same mean of the slots' colours, stored as fp32 (rgb_f32 != 0) or
+ *     rounded half to even and clamped to a byte.  normals: g[axis] = the sum in edge order of (d1 - d0) over the axis' four edges,
+ *     len = sqrtf((g0 * g0 + g1 * g1) + g2 * g2), g / len, or (0, 0, 0) when len is not finite and positive; it points to the positive side.
+ *   Faces: a live slot with (u, v) = ((axis + 1) % 3, (axis + 2) % 3) and voxel c yields one quad when the cells q0 = c - e_u - e_v,
+ *     q1 = c - e_v, q2 = c, q3 = c - e_u exist and are live.  Winding (q0, q1, q2, q3) when tsdf[c] < 0, else (q0, q3, q2, q1): the
+ *     geometric normal points to the positive side.  The quad (a, b, c, d) becomes the triangles (a, b, c) and (a, c, d), rows 2r and
+ *     2r + 1 of quad r; volumes in batch order, then slots ascending.  The indices are int32 vertex rows LOCAL to the volume (the row
+ *     minus vert_offsets[b]).  A live cell none of whose quads is complete leaves an unreferenced vertex.
+ *   outputs: vert_counts / face_counts int64 [B] and vert_offsets / face_offsets int64 [B+1] are always written, with the TRUE totals
+ *     (faces in triangles) whatever the capacities are.  vertices fp32 [vert_capacity,3], rgb [vert_capacity,3] u8 or fp32 (optional,
+ *     needs color and vertices), normals fp32 [vert_capacity,3] (optional, needs vertices): the rows r < min(total, vert_capacity).  faces
+ *     int32 [face_capacity,3]: a quad is written only when both its triangles lie below face_capacity.  vertices == NULL or
+ *     vert_capacity == 0, faces == NULL or face_capacity == 0: that part is counted only.  Absent outputs are never touched.
+ *   work: device scratch of at least ud_tsdf_mesh_work_bytes(B, Nx, Ny, Nz) bytes (host-only query; -1 outside the limits), 8-byte
+ *     aligned, work_bytes its size.  Its contents need no initialisation.
+ *   Limits: UdTsdfPoints'.  Every refusal is returned before any HIP call.  Built with -ffp-contract=off. */
+typedef struct UdTsdfMesh {
+  const float* tsdf; const float* weight; const float* color; const float* origin;
+  float* vertices; void* rgb; float* normals; int* faces;
+  long long* vert_counts; long long* vert_offsets; long long* face_counts; long long* face_offsets;
+  void* work; long long work_bytes;
+  long long vert_capacity, face_capacity;
+  int B, Nx, Ny, Nz, n_origin, rgb_f32, voxel_size_bits, min_weight_bits;
+} UdTsdfMesh;
+int ud_tsdf_mesh(const UdTsdfMesh* desc, void* stream);
+long long ud_tsdf_mesh_work_bytes(int B, int Nx, int Ny, int Nz);
+
 /* A TSDF volume ray-cast to depth, points, normals and colour in ONE launch (csrc/tsdf_render.hip; the arithmetic of a ray is
  * csrc/tsdf_ray.h, where the definition is written out operation by operation): one thread per output pixel marches K samples through
  * the volume, reads the distance trilinearly and stops at the first crossing seen from the front.  No workspace, no atomics, no LDS, no
@@ -1225,7 +1262,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41, UdTsdfIntegrate = 43, UdTsdfPoints = 44, UdTsdfRender = 45; 16, 19, 22, 24, 26, 30, 32, 35, 37, 40 and 42 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41, UdTsdfIntegrate = 43, UdTsdfPoints = 44, UdTsdfRender = 45, UdTsdfMesh = 46; 16, 19, 22, 24, 26, 30, 32, 35, 37, 40 and 42 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

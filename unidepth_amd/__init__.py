@@ -19,8 +19,9 @@ _WARP = ("warp_camera",)
 _NORMALS = ("normals_from_points", "normals_camera", "eval_normals")
 _CONSISTENCY = ("depth_consistency", "depth_consistency_composition", "invert_rigid")
 _TSDF = ("TsdfVolume", "tsdf_integrate", "tsdf_integrate_composition", "tsdf_points", "tsdf_render", "tsdf_render_composition")
+_TSDFMESH = ("TriangleMesh", "tsdf_mesh", "tsdf_mesh_composition", "save_mesh_ply")
 __all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP, *_WARP, *_NORMALS,
-           *_CONSISTENCY, *_TSDF]
+           *_CONSISTENCY, *_TSDF, *_TSDFMESH]
 
 
 def __getattr__(name):
@@ -66,4 +67,7 @@ def __getattr__(name):
     if name in _TSDF:                                 # depth views fused into a TSDF volume, and its surface as points (tsdf.py, csrc/tsdf.hip)
         from . import tsdf
         return getattr(tsdf, name)
+    if name in _TSDFMESH:                             # a TSDF volume's surface as a triangle mesh (tsdfmesh.py, csrc/tsdf_mesh.hip)
+        from . import tsdfmesh
+        return getattr(tsdfmesh, name)
     raise AttributeError(name)

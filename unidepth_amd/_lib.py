@@ -174,6 +174,14 @@ class UdTsdfPoints(C.Structure):
                 ("min_weight_bits", i32)]
 
 
+class UdTsdfMesh(C.Structure):
+    _fields_ = [("tsdf", vp), ("weight", vp), ("color", vp), ("origin", vp), ("vertices", vp), ("rgb", vp), ("normals", vp), ("faces", vp),
+                ("vert_counts", vp), ("vert_offsets", vp), ("face_counts", vp), ("face_offsets", vp), ("work", vp), ("work_bytes", i64),
+                ("vert_capacity", i64), ("face_capacity", i64),
+                ("B", i32), ("Nx", i32), ("Ny", i32), ("Nz", i32), ("n_origin", i32), ("rgb_f32", i32), ("voxel_size_bits", i32),
+                ("min_weight_bits", i32)]
+
+
 class UdTsdfRender(C.Structure):
     _fields_ = [("tsdf", vp), ("weight", vp), ("color", vp), ("origin", vp), ("T", vp), ("params", vp), ("rays", vp),
                 ("depth", vp), ("valid", vp), ("points", vp), ("normals", vp), ("color_out", vp),
@@ -390,6 +398,7 @@ def _load():
         "ud_tsdf_integrate": [P(UdTsdfIntegrate), vp],
         "ud_tsdf_points": [P(UdTsdfPoints), vp],
         "ud_tsdf_render": [P(UdTsdfRender), vp],
+        "ud_tsdf_mesh": [P(UdTsdfMesh), vp],
         "ud_eval_normals": [P(UdEvalNormals), vp, i64, vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
@@ -421,11 +430,13 @@ def _load():
     lib.ud_pointcloud_work_bytes.restype = i64
     lib.ud_tsdf_points_work_bytes.argtypes = [i32, i32, i32, i32]
     lib.ud_tsdf_points_work_bytes.restype = i64
+    lib.ud_tsdf_mesh_work_bytes.argtypes = [i32, i32, i32, i32]
+    lib.ud_tsdf_mesh_work_bytes.restype = i64
     lib.ud_colorize_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency, None, UdTsdfIntegrate, UdTsdfPoints, UdTsdfRender]):
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency, None, UdTsdfIntegrate, UdTsdfPoints, UdTsdfRender, UdTsdfMesh]):
         if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35, 37, 40 and 42 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:

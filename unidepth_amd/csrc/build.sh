@@ -64,6 +64,9 @@ done
 # tsdf_render: the march, the trilinear reads, the crossing, the gradient and the colour of a ray are defined operation by operation in fp32
 # (tsdf_ray.h under this flag is what the numpy fp32 restatement and the host build of the tests compute), same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c tsdf_render.hip -o $BD/tsdf_render.o ) & pids+=($!)
+# tsdf_mesh: a vertex is the mean of its cell's crossings (tsdf_mesh_point.h calls tsdf_point.h's ud_tsdf_slot), summed in a fixed order,
+# and must have the bits of the numpy fp32 restatement and of the host build of the tests, same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c tsdf_mesh.hip -o $BD/tsdf_mesh.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)

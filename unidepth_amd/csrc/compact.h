@@ -1,4 +1,4 @@
-// The ordered stream compaction that pointcloud.hip (pixels), tsdf.hip (slots) and eval3d.hip (samples) share: a mask of items becomes a
+// The ordered stream compaction that pointcloud.hip (pixels), tsdf.hip (slots), tsdf_mesh.hip (cells, slots) and eval3d.hip (samples) share: a mask of items becomes a
 // packed list in item order, every bit fixed.  Device and host inline code; each file keeps its predicate, its row writer, its thin
 // __global__ wrappers and its entry point.
 //
@@ -8,6 +8,8 @@
 //   cp_flag        predicate per item -> the tile's 16 words and its popcount; items at or beyond n are predicate = false
 //   cp_scan_sweep  exclusive scan by one workgroup of CP_SCAN threads, swept in chunks of CP_SCAN with a carry
 //   cp_pack        emit(item, row inside the tile) for every set bit: row = popcount of the earlier words + of the lower lanes
+//   cp_test / cp_rank   for a second packer that reads the finished mask of a first (tsdf_mesh.hip): the bit of an item, and the item's row
+//                  inside its member from tile_offs and popcounts.  Plain per-lane reads, no barrier: callable from a predicate or an emit
 // The contract.  Every thread of the workgroup calls the helper, from uniform control flow: cp_flag holds a ballot per step and a
 // barrier, cp_scan_sweep two barriers per chunk, cp_pack wave-wide shuffles.  A caller may return BEFORE the call when the whole
 // workgroup does (eval3d.hip's surplus tiles), never a single lane; the predicate and emit run divergently and must hold no barrier.
@@ -124,6 +126,20 @@ __device__ __forceinline__ void cp_pack(const unsigned long long* words, int t, 
     const int before = __shfl(my_before, k, UD_WAVE);
     if ((m >> lane) & 1ull) emit(t * CP_TILE + k * UD_WAVE + lane, before + __popcll(m & ((1ull << lane) - 1ull)));
   }
+}
+
+// ---- a second packer reading the mask of a first (tsdf_mesh.hip: a face asks for its four vertices), after the first one's flag kernel
+// and scans.  words: the 16 * nT words of ONE member, tile_offs: its nT entries; by the index map item p is bit p & 63 of word p >> 6.
+__device__ __forceinline__ bool cp_test(const unsigned long long* words, long long item) { return (words[item >> 6] >> (item & 63)) & 1ull; }
+
+// The row of a kept item inside its member: the kept items of the earlier tiles, of the tile's earlier words and of the word's lower bits.
+__device__ __forceinline__ int cp_rank(const unsigned long long* words, const int* tile_offs, long long item) {
+  const long long t = item / CP_TILE;
+  const int k = (int)(item >> 6) & (CP_WORDS - 1);
+  const unsigned long long* w = words + t * CP_WORDS;
+  int r = tile_offs[t] + __popcll(w[k] & ((1ull << (item & 63)) - 1ull));
+  for (int j = 0; j < k; ++j) r += __popcll(w[j]);
+  return r;
 }
 
 // ---- the two scans of a packer whose result is counts / offsets (pointcloud.hip, tsdf.hip), launched after its flag kernel.  Templates,

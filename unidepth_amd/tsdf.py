@@ -8,6 +8,7 @@ depth_consistency when N predicted depth maps, their cameras and their poses bec
     tsdf_render(volume, camera, size, ...)  the volume ray-cast from a camera: depth, valid, points, normals, colour (ud_tsdf_render,
                                             csrc/tsdf_render.hip); TsdfVolume.render forwards to it
     tsdf_render_composition(...)            the same definition spelled in torch, a loop over the samples of the march
+    TsdfVolume.mesh(...)                    the surface as an indexed triangle mesh: tsdfmesh.tsdf_mesh (ud_tsdf_mesh, csrc/tsdf_mesh.hip)
 
 For every voxel and every view, in view order: the voxel's centre moved into the view and projected, the view's depth read at the nearest
 pixel, sdf = that depth - the centre's own depth, and where the pixel is valid and the voxel not further than `trunc` behind the surface,
@@ -46,6 +47,11 @@ class TsdfVolume:
     def render(self, camera, size, transforms=None, **kw):
         """tsdf_render(self, camera, size, transforms, **kw)"""
         return tsdf_render(self, camera, size, transforms, **kw)
+
+    def mesh(self, **kw):
+        """tsdfmesh.tsdf_mesh(self, **kw): the surface as an indexed triangle mesh"""
+        from .tsdfmesh import tsdf_mesh
+        return tsdf_mesh(self, **kw)
 
 
 def _positive(fn, name, x):
