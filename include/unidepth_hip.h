@@ -876,6 +876,51 @@ typedef struct UdTsdfMesh {
 int ud_tsdf_mesh(const UdTsdfMesh* desc, void* stream);
 long long ud_tsdf_mesh_work_bytes(int B, int Nx, int Ny, int Nz);
 
+/* Frame-to-model point-to-plane ICP, one Gauss-Newton step in TWO launches (csrc/icp.hip; the arithmetic is csrc/icp_point.h, which only
+ * calls csrc/camera_models.h and csrc/remap_taps.h): a depth frame, or a point map, aligned to the point and normal maps of a model view
+ * (what ud_tsdf_render returns) under the current estimate T, frame camera to model camera.  KinectFusion's tracking step.
+ *   Frame pixel i = y * W + x of image b: depth fp32 [B,H,W] with params fp32 [B,16] and model_frame[b] (closed-form models only: Pinhole,
+ *     EUCM, Spherical, MEI), or points fp32 [B,3,H,W] in its place (exactly one of the two; the route of OPENCV / Fisheye624 frames).
+ *     p = ud_reconstruct's point of the pixel centre (x + 0.5, y + 0.5), or the point as given.  live = depth > 0 (points: every component
+ *     finite) && mask[b,i] != 0 (uint8, optional) && weights[b,i] > 0 and finite (fp32, optional; w = 1 without).
+ *   q = T p, ud_camera_project's arithmetic; (u, v) = the projection of q through params_model fp32 [B,16], model_model[b] (any of the six);
+ *     usable = the model's in-image test against (Hm, Wm) && the model's depth of q > 0 && u, v finite.
+ *   The model at the nearest pixel (ud_remap's nearest tap, zeros padding): m = model_points, n = model_normals fp32 [B,3,Hm,Wm], read only
+ *     where the tap is in range and model_valid uint8 [B,Hm,Wm] != 0 (0 otherwise); the model pixel is valid then if also 0 <= u <= Wm and
+ *     0 <= v <= Hm.
+ *   e = m - q; d2 = (e0*e0 + e1*e1) + e2*e2; r = (n0*e0 + n1*e1) + n2*e2; c = q x n (c0 = q1*n2 - q2*n1, cyclic); every operation rounded
+ *     separately in fp32.  matched = live && usable && model pixel valid && n != 0 && d2 <= dist_tol * dist_tol && (with normals fp32
+ *     [B,3,H,W] and has_cos: (R_T nf) . n >= cos_tol, products summed left to right) && r, c, n finite; false whenever a NaN is compared.
+ *   The row g = (c0, c1, c2, n0, n1, n2).  Optional per-pixel outputs matched uint8 [B,H,W], residual fp32 [B,H,W], rows fp32 [B,6,H,W]:
+ *     exactly 0 where not matched.
+ *   system fp64 [B,32], over the matched pixels: gw_i = (double)w * (double)g_i; A_ij += gw_i * (double)g_j for i <= j (slots 0..20, the
+ *     upper triangle row-major), b_i += gw_i * (double)r (21..26), e += ((double)w * (double)r) * (double)r (27), wsum (28), count (29,
+ *     exact), 30 and 31 zero.  Summed in a fixed order -- a thread's pixels in order, the wave's threads by the xor butterfly, the waves in
+ *     order, the workgroups in index order: no floating-point atomics, the bits do not depend on scheduling or on the workspace's contents.
+ *   work: device scratch of at least ud_icp_workspace_bytes(B, H, W) bytes (host-only query; -1 outside the limits), 8-byte aligned, holding
+ *     the workgroups' partials [B, nblk, 32], nblk = min(ceil(H * W / 256), 256) workgroups per image.  blocks != 0 replaces the 256 (at
+ *     most 1024, which is what the workspace is sized for): another order of summation, for measurement.
+ *   solve != 0: the second launch also solves (A + damping I) x = b by LDL^T without pivoting in fp64 (+ - * / only) and, when count >=
+ *     min_count, every pivot > 0 and x finite (status 1), sets T[b] = [R R_old | R t_old + v] in place with R the Cayley map of omega / 2,
+ *     formed in fp64 and rounded to fp32 once; status 0 leaves T[b] as it was and x = 0.  It needs nT = B.  x fp64 [B,6], status uint8 [B]
+ *     and stats fp64 (4 values e, wsum, count, status at stats + b * stats_stride) are optional.  The order of every operation is fixed in
+ *     the comments of csrc/icp_point.h.  damping_bits holds the bit pattern of the fp64 damping, dist_tol_bits / cos_tol_bits those of the
+ *     fp32 tolerances.
+ *   ud_icp_update: the second launch alone, on a given system (T, system, nT = B, damping, min_count, x, status, stats are read).
+ *   Limits: 1 <= B <= UD_RECON_MAX_B; H, W, Hm, Wm >= 1; 6 * H * W and 3 * Hm * Wm < 2^31 - 256; nT 1 or B; dist_tol and damping finite and
+ *   >= 0; -1 <= cos_tol <= 1; min_count >= 0; 0 <= blocks <= 1024.  Every refusal is returned before any HIP call.  Built with -ffp-contract=off. */
+typedef struct UdIcp {
+  const float* depth; const float* points; const float* params; const unsigned char* mask; const float* weights; const float* normals;
+  const float* model_points; const float* model_normals; const unsigned char* model_valid; const float* params_model;
+  float* T; void* work; double* system; unsigned char* matched; float* residual; float* rows; double* x; unsigned char* status; double* stats;
+  long long work_bytes, stats_stride, damping_bits;
+  int B, H, W, Hm, Wm, nT, solve, min_count, has_cos, dist_tol_bits, cos_tol_bits, blocks;
+  unsigned char model_frame[UD_RECON_MAX_B], model_model[UD_RECON_MAX_B];
+} UdIcp;
+int ud_icp_linearize(const UdIcp* desc, void* stream);
+int ud_icp_update(const UdIcp* desc, void* stream);
+long long ud_icp_workspace_bytes(int B, int H, int W);
+
 /* A TSDF volume ray-cast to depth, points, normals and colour in ONE launch (csrc/tsdf_render.hip; the arithmetic of a ray is
  * csrc/tsdf_ray.h, where the definition is written out operation by operation): one thread per output pixel marches K samples through
  * the volume, reads the distance trilinearly and stops at the first crossing seen from the front.  No workspace, no atomics, no LDS, no
@@ -1262,7 +1307,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41, UdTsdfIntegrate = 43, UdTsdfPoints = 44, UdTsdfRender = 45, UdTsdfMesh = 46; 16, 19, 22, 24, 26, 30, 32, 35, 37, 40 and 42 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41, UdTsdfIntegrate = 43, UdTsdfPoints = 44, UdTsdfRender = 45, UdTsdfMesh = 46, UdIcp = 48; 16, 19, 22, 24, 26, 30, 32, 35, 37, 40, 42 and 47 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

@@ -20,8 +20,9 @@ _NORMALS = ("normals_from_points", "normals_camera", "eval_normals")
 _CONSISTENCY = ("depth_consistency", "depth_consistency_composition", "invert_rigid")
 _TSDF = ("TsdfVolume", "tsdf_integrate", "tsdf_integrate_composition", "tsdf_points", "tsdf_render", "tsdf_render_composition")
 _TSDFMESH = ("TriangleMesh", "tsdf_mesh", "tsdf_mesh_composition", "save_mesh_ply")
+_ICP = ("icp_linearize", "icp_linearize_composition", "icp_solve", "track_camera", "track_camera_composition")
 __all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP, *_WARP, *_NORMALS,
-           *_CONSISTENCY, *_TSDF, *_TSDFMESH]
+           *_CONSISTENCY, *_TSDF, *_TSDFMESH, *_ICP]
 
 
 def __getattr__(name):
@@ -70,4 +71,7 @@ def __getattr__(name):
     if name in _TSDFMESH:                             # a TSDF volume's surface as a triangle mesh (tsdfmesh.py, csrc/tsdf_mesh.hip)
         from . import tsdfmesh
         return getattr(tsdfmesh, name)
+    if name in _ICP:                                  # camera tracking against a model view: point-to-plane ICP (icp.py, csrc/icp.hip)
+        from . import icp
+        return getattr(icp, name)
     raise AttributeError(name)

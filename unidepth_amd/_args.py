@@ -1,4 +1,4 @@
-"""The argument checks the camera-map wrappers share (gtpoints, unproject, reproject, remap, warp, normals, consistency, tsdf): one sentence
+"""The argument checks the camera-map wrappers share (gtpoints, unproject, reproject, remap, warp, normals, consistency, tsdf, icp): one sentence
 per kind of fault, every message prefixed with the public name `fn` of the caller and naming the argument.  Nothing here touches the
 device or launches anything; conversions stay in the wrappers."""
 from __future__ import annotations

@@ -190,6 +190,16 @@ class UdTsdfRender(C.Structure):
                 ("min_weight_bits", i32), ("model", C.c_ubyte * UD_RECON_MAX_B)]
 
 
+class UdIcp(C.Structure):
+    _fields_ = [("depth", vp), ("points", vp), ("params", vp), ("mask", vp), ("weights", vp), ("normals", vp),
+                ("model_points", vp), ("model_normals", vp), ("model_valid", vp), ("params_model", vp),
+                ("T", vp), ("work", vp), ("system", vp), ("matched", vp), ("residual", vp), ("rows", vp), ("x", vp), ("status", vp), ("stats", vp),
+                ("work_bytes", i64), ("stats_stride", i64), ("damping_bits", i64),
+                ("B", i32), ("H", i32), ("W", i32), ("Hm", i32), ("Wm", i32), ("nT", i32), ("solve", i32), ("min_count", i32), ("has_cos", i32),
+                ("dist_tol_bits", i32), ("cos_tol_bits", i32), ("blocks", i32),
+                ("model_frame", C.c_ubyte * UD_RECON_MAX_B), ("model_model", C.c_ubyte * UD_RECON_MAX_B)]
+
+
 UD_EVAL_NORMALS_MAX_T = 8
 
 
@@ -399,6 +409,8 @@ def _load():
         "ud_tsdf_points": [P(UdTsdfPoints), vp],
         "ud_tsdf_render": [P(UdTsdfRender), vp],
         "ud_tsdf_mesh": [P(UdTsdfMesh), vp],
+        "ud_icp_linearize": [P(UdIcp), vp],
+        "ud_icp_update": [P(UdIcp), vp],
         "ud_eval_normals": [P(UdEvalNormals), vp, i64, vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
@@ -432,12 +444,14 @@ def _load():
     lib.ud_tsdf_points_work_bytes.restype = i64
     lib.ud_tsdf_mesh_work_bytes.argtypes = [i32, i32, i32, i32]
     lib.ud_tsdf_mesh_work_bytes.restype = i64
+    lib.ud_icp_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.ud_icp_workspace_bytes.restype = i64
     lib.ud_colorize_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency, None, UdTsdfIntegrate, UdTsdfPoints, UdTsdfRender, UdTsdfMesh]):
-        if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35, 37, 40 and 42 are not assigned: the library answers -1
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency, None, UdTsdfIntegrate, UdTsdfPoints, UdTsdfRender, UdTsdfMesh, None, UdIcp]):
+        if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35, 37, 40, 42 and 47 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)

@@ -10,7 +10,7 @@ void ud_set_error(const char* msg) {
 }
 
 extern "C" const char* ud_last_error(void) { return g_err; }
-extern "C" int ud_version(void) { return 127; }
+extern "C" int ud_version(void) { return 128; }
 
 // struct sizes, so the Python binding can verify its ctypes mirror of include/unidepth_hip.h
 extern "C" int ud_struct_size(int which) {
@@ -51,6 +51,7 @@ extern "C" int ud_struct_size(int which) {
     case 44: return (int)sizeof(UdTsdfPoints);
     case 45: return (int)sizeof(UdTsdfRender);
     case 46: return (int)sizeof(UdTsdfMesh);
+    case 48: return (int)sizeof(UdIcp);              // 47 stays unassigned (-1)
     default: return -1;
   }
 }

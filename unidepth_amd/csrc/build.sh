@@ -67,6 +67,10 @@ done
 # tsdf_mesh: a vertex is the mean of its cell's crossings (tsdf_mesh_point.h calls tsdf_point.h's ud_tsdf_slot), summed in a fixed order,
 # and must have the bits of the numpy fp32 restatement and of the host build of the tests, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c tsdf_mesh.hip -o $BD/tsdf_mesh.o ) & pids+=($!)
+# icp: unproject, project, the nearest-pixel remap, the residual and the row fused per pixel (icp_point.h calls camera_models.h and
+# remap_taps.h), each per-pixel output with the bits of those launches run one after the other; the fp64 sums and the LDL^T / Cayley solve
+# round every operation once, so the numpy fp64 restatement and the host build of the tests have the solve's bits, same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c icp.hip -o $BD/icp.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)

@@ -53,6 +53,37 @@ class TsdfVolume:
         from .tsdfmesh import tsdf_mesh
         return tsdf_mesh(self, **kw)
 
+    def track(self, depth, camera, size, transform, *, near, far, step=None, min_weight=1.0, **kw):
+        """The pose of a new depth frame from the volume: the volume rendered at the prior pose -- self.render(camera, size, transform,
+        near=near, far=far, return_points=True, return_normals=True) -- and icp.track_camera(depth, camera, points, normals, valid, camera,
+        None, **kw) from the identity against that prediction (dist_tol is required; iters, cos_tol, normals, mask, weights, damping and
+        min_count as there).
+
+        transform   fp32 [4,4], [3,4] or [B,4,4] / [B,3,4]: the PRIOR pose, VOLUME (world) TO CAMERA coordinates, tsdf_integrate's and
+                    tsdf_render's convention; for a video, the pose of the frame before.
+        size        (H, W) of the rendered prediction; the depth frame may have another size when its camera says so.
+
+        ->  (T_new fp32 [B,3,4], stats fp64 [B,iters,4]): the frame's pose, VOLUME (world) TO CAMERA coordinates again, so that
+            tsdf_integrate(self, depth[:, None], [camera], T_new[:, None], ...) integrates the frame as it is.  track_camera's estimate
+            E maps the frame camera to the prior camera, so T_new = invert_rigid(E) . transform, composed element-wise in fp32: row i of
+            the product is ((a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j), plus a_i3 in the last column.  stats as track_camera returns them."""
+        from .icp import track_camera
+        fn = "TsdfVolume.track"
+        B = _check_volume(fn, self)[0]
+        _, valid, points, normals = self.render(camera, size, transform, near=near, far=far, step=step, min_weight=min_weight,
+                                                return_points=True, return_normals=True)
+        E, stats = track_camera(depth, camera, points, normals, valid, camera, None, **kw)
+        A = invert_rigid(E)
+        if transform is None:
+            return A, stats
+        Bm = transform[..., :3, :].reshape(-1, 3, 4)
+        a = lambda i, j: A[:, i, j:j + 1]                            # noqa: E731
+        rows = []
+        for i in range(3):
+            row = (a(i, 0) * Bm[:, 0] + a(i, 1) * Bm[:, 1]) + a(i, 2) * Bm[:, 2]
+            rows.append(torch.cat([row[:, :3], row[:, 3:4] + a(i, 3)], dim=1))
+        return torch.stack(rows, dim=1).expand(B, 3, 4).contiguous(), stats
+
 
 def _positive(fn, name, x):
     """a Python number as (the value of its fp32 rounding, that rounding's bit pattern); the rounded value is finite and > 0"""
