@@ -330,13 +330,17 @@ def test_track_camera_against_the_composition(kind, key):
 VOLUME = dict(grid_shape=(48, 40, 40), voxel_size=0.078125, origin=(-1.5, -1.9, 0.0), trunc=0.25)
 # x in -1.5 .. 1.625, y in -1.9 .. 1.225, z in 0 .. 3.75: the planes x = -1.2, y = 1.0 and z = 3.0 lie 3.8, 2.9 and 9.6 voxels inside
 POSE_SIDE = ic.pose((0.0, 0.3, 0.0), (-0.5, 0.0, 0.2)) @ ic.POSE_A
+# what TsdfVolume.track reaches in the test below (rotation error in degrees, translation error against POSE_B), measured on the MI355X
+# and rounded up in the last digit: the floor of the discretised surface (profiles/scene_truth.txt)
+END_TO_END_MEASURED = (0.0679, 0.000998)
 
 
 def test_volume_track_end_to_end():
     """the corner fused by tsdf_integrate from the views A and one sideways (96x128, f 80) into a 40x40x48 grid of 5/64 voxels at
     (-1.5, -1.9, 0), trunc 0.25; rendered at A (48x64, f 40), the frame from B: the volume->camera transform returned is closer to B than
     the start A in rotation and in translation (the start: 3.08 degrees, 0.0707), and integrating the frame with it changes the volume.
-    The errors reached are printed; no bar beyond "closer" is set: the floor of the discretised surface is not known."""
+    The errors reached are printed and held under a bar measured against the analytic truth (tests/test_scene_truth_gpu.py measures
+    the whole chain the same way)."""
     from unidepth_amd import tsdf
     Hs, Ws, fs = 96, 128, 80.0
     views = np.stack([ic.corner_view(P, Hs, Ws, fs)[0] for P in (ic.POSE_A, POSE_SIDE)]).astype(np.float32)
@@ -352,6 +356,16 @@ def test_volume_track_end_to_end():
     start, reached = ic.pose_errors(ic.POSE_A, ic.POSE_B), ic.pose_errors(T[0].cpu().numpy(), ic.POSE_B)
     print(f"TsdfVolume.track: start {start}, reached {reached}, matched {stats[0, :, 2].tolist()}")
     assert reached[0] < start[0] and reached[1] < start[1], (start, reached)
+    # the bar on the reached pose: 1.5 times what the correct chain measures against the analytic truth POSE_B (END_TO_END_MEASURED);
+    # the same result composed the wrong way round, E . prior for invert_rigid(E) . prior, must lie at least twice the bar away
+    bar = tuple(1.5 * m for m in END_TO_END_MEASURED)
+    assert reached[0] <= bar[0] and reached[1] <= bar[1], (reached, bar)
+    got, A = np.eye(4), np.eye(4)
+    got[:3], A[:3] = T[0].cpu().numpy(), ic.POSE_A[:3]
+    E = A @ np.linalg.inv(got)                                       # got = E^-1 prior
+    wrong = ic.pose_errors(E @ A, ic.POSE_B)
+    print(f"TsdfVolume.track: composed the wrong way round {wrong}, bar {bar}")
+    assert wrong[0] >= 2 * bar[0] and wrong[1] >= 2 * bar[1], (wrong, bar)
     before = vol.tsdf.clone()
     tsdf.tsdf_integrate(vol, frame, [cam], T[None], trunc=VOLUME["trunc"])
     assert not torch.equal(before, vol.tsdf)
