@@ -921,6 +921,31 @@ int ud_icp_linearize(const UdIcp* desc, void* stream);
 int ud_icp_update(const UdIcp* desc, void* stream);
 long long ud_icp_workspace_bytes(int B, int H, int W);
 
+/* The depth pyramid of a batch in ONE launch (csrc/pyramid.hip; the arithmetic of a pixel is csrc/pyramid_point.h, where the definition is
+ * written out operation by operation): an edge-preserving bilateral filter at level 0 and gated 2 x 2 means for levels 1 .. levels - 1,
+ * what a coarse-to-fine tracker runs between the depth prediction and ud_icp_linearize.
+ *   depth fp32 [B,H,W]; mask uint8 [B,H,W] (optional); weights fp32 [B,H,W] (optional).  A pixel is live when mask != 0 and
+ *   0 < depth < +inf and, with weights, 0 < w < +inf (false for a NaN).  A pixel that is not live is 0 at every level.
+ *   Level 0, radius r = 0: the live depths.  r >= 1: over the live taps inside the image, dy = -r..r (outer), dx = -r..r (inner):
+ *   delta = |d - dc|, bin = delta * inv_bin >= 256 ? 255 : (int)(delta * inv_bin), w = ws[(dy+r)(2r+1) + dx+r] * wr[bin], num += w * d,
+ *   den += w, out = num / den.  ws fp32 [(2r+1)^2] and wr fp32 [256] are DEVICE pointers; the caller keeps ws[centre] > 0 and wr[0] > 0
+ *   (den > 0 follows); inv_bin_bits is the bit pattern of the fp32 inv_bin.  The level-0 weight is the centre's where live, else 0.
+ *   Level l >= 1: H_l = H_{l-1} / 2, W_l = W_{l-1} / 2 (an odd last row or column is dropped); the members (2y,2x), (2y,2x+1),
+ *   (2y+1,2x), (2y+1,2x+1) of level l - 1 are live where > 0; anchor = the smallest live member; a member is included when live and
+ *   d - anchor <= gate (gate_bits: the fp32's bit pattern, >= 0, +inf allowed); value = the included members summed in that order / their
+ *   count, weight = their weights summed likewise / the same count; 0 when no member is live.
+ *   out_depth[l] fp32 [B,H_l,W_l], out_weights[l] likewise (read only with weights): a NULL pointer means that level is not written.
+ *   tile: the level-0 tile of a workgroup, 0 = the default, 1 = 32 x 32, 2 = 64 x 16; the result does not depend on it.
+ *   No workspace, no atomics, no host synchronisation: captures into a graph.
+ *   Limits: 1 <= B <= UD_RECON_MAX_B, 1 <= levels <= 4, H, W >= 2^(levels-1), H * W < 2^31 - 256, 0 <= radius <= 4, gate >= 0 and not a
+ *   NaN, inv_bin finite and > 0 (with a radius).  Every refusal is returned before any HIP call.  Built with -ffp-contract=off. */
+typedef struct UdDepthPyramid {
+  const float* depth; const unsigned char* mask; const float* weights; const float* ws; const float* wr;
+  float* out_depth[4]; float* out_weights[4];
+  int B, H, W, levels, radius, tile, gate_bits, inv_bin_bits;
+} UdDepthPyramid;
+int ud_depth_pyramid(const UdDepthPyramid* desc, void* stream);
+
 /* A TSDF volume ray-cast to depth, points, normals and colour in ONE launch (csrc/tsdf_render.hip; the arithmetic of a ray is
  * csrc/tsdf_ray.h, where the definition is written out operation by operation): one thread per output pixel marches K samples through
  * the volume, reads the distance trilinearly and stops at the first crossing seen from the front.  No workspace, no atomics, no LDS, no
@@ -1307,7 +1332,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
 /* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
- * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41, UdTsdfIntegrate = 43, UdTsdfPoints = 44, UdTsdfRender = 45, UdTsdfMesh = 46, UdIcp = 48; 16, 19, 22, 24, 26, 30, 32, 35, 37, 40, 42 and 47 are not assigned and answer -1 like every unknown
+ * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41, UdTsdfIntegrate = 43, UdTsdfPoints = 44, UdTsdfRender = 45, UdTsdfMesh = 46, UdIcp = 48, UdDepthPyramid = 49; 16, 19, 22, 24, 26, 30, 32, 35, 37, 40, 42 and 47 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);
 int ud_struct_size(int which);

@@ -21,8 +21,9 @@ _CONSISTENCY = ("depth_consistency", "depth_consistency_composition", "invert_ri
 _TSDF = ("TsdfVolume", "tsdf_integrate", "tsdf_integrate_composition", "tsdf_points", "tsdf_render", "tsdf_render_composition")
 _TSDFMESH = ("TriangleMesh", "tsdf_mesh", "tsdf_mesh_composition", "save_mesh_ply")
 _ICP = ("icp_linearize", "icp_linearize_composition", "icp_solve", "track_camera", "track_camera_composition")
+_PYRAMID = ("DepthFilter", "prepare_depth_filter", "depth_pyramid", "depth_pyramid_composition", "pyramid_cameras", "track_camera_pyramid")
 __all__ = ["UniDepthV2", "UniDepthV1", "UniDepth", *_POINTCLOUD, *_MATCHING, *_VISUALIZATION, *_REPROJECT, *_TESTPREP, *_GTPOINTS, *_UNPROJECT, *_REMAP, *_WARP, *_NORMALS,
-           *_CONSISTENCY, *_TSDF, *_TSDFMESH, *_ICP]
+           *_CONSISTENCY, *_TSDF, *_TSDFMESH, *_ICP, *_PYRAMID]
 
 
 def __getattr__(name):
@@ -74,4 +75,7 @@ def __getattr__(name):
     if name in _ICP:                                  # camera tracking against a model view: point-to-plane ICP (icp.py, csrc/icp.hip)
         from . import icp
         return getattr(icp, name)
+    if name in _PYRAMID:                              # depth filter, pyramid and coarse-to-fine tracking (pyramid.py, csrc/pyramid.hip)
+        from . import pyramid
+        return getattr(pyramid, name)
     raise AttributeError(name)

@@ -163,6 +163,42 @@ def tolerance(fn, name, x):
     return val, bits
 
 
+def positive(fn, name, x) -> float:
+    """a Python number that is finite and > 0 -> float"""
+    try:
+        v = float(x)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: {name} must be a number") from None
+    if isinstance(x, bool) or not (v > 0.0 and math.isfinite(v)):
+        raise ValueError(f"{fn}: {name} must be finite and positive, got {x}")
+    return v
+
+
+def gate(fn, name, x) -> int:
+    """a Python number as the bit pattern of its fp32 rounding; the rounded value is >= 0, +inf allowed, not a NaN"""
+    try:
+        v = float(x)
+        bits = f32_bits(v) if math.isfinite(v) else f32_bits(math.copysign(math.inf, v)) if not math.isnan(v) else None
+    except (TypeError, ValueError, OverflowError, struct.error):
+        raise ValueError(f"{fn}: {name} must be a number in fp32's range or inf") from None
+    if isinstance(x, bool) or bits is None or not v >= 0.0:
+        raise ValueError(f"{fn}: {name} must not be negative or a NaN, got {x}")
+    return bits
+
+
+def radius(fn, r, most):
+    if isinstance(r, bool) or not isinstance(r, int) or not 0 <= r <= most:
+        raise ValueError(f"{fn}: radius must be an integer in 0 .. {most}, got {r!r}")
+
+
+def levels(fn, L, H, W, most):
+    """a pyramid of L levels over (H, W) images: every level keeps at least one pixel"""
+    if isinstance(L, bool) or not isinstance(L, int) or not 1 <= L <= most:
+        raise ValueError(f"{fn}: levels must be an integer in 1 .. {most}, got {L!r}")
+    if min(H, W) < 2 ** (L - 1):
+        raise ValueError(f"{fn}: {L} levels need H, W >= {2 ** (L - 1)}, got H={H} W={W}")
+
+
 def max_images(fn, B):
     if B > _lib.UD_RECON_MAX_B:
         raise ValueError(f"{fn}: at most {_lib.UD_RECON_MAX_B} images per call, got {B}")

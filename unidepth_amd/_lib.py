@@ -200,6 +200,12 @@ class UdIcp(C.Structure):
                 ("model_frame", C.c_ubyte * UD_RECON_MAX_B), ("model_model", C.c_ubyte * UD_RECON_MAX_B)]
 
 
+class UdDepthPyramid(C.Structure):
+    _fields_ = [("depth", vp), ("mask", vp), ("weights", vp), ("ws", vp), ("wr", vp), ("out_depth", vp * 4), ("out_weights", vp * 4),
+                ("B", i32), ("H", i32), ("W", i32), ("levels", i32), ("radius", i32), ("tile", i32), ("gate_bits", i32),
+                ("inv_bin_bits", i32)]
+
+
 UD_EVAL_NORMALS_MAX_T = 8
 
 
@@ -411,6 +417,7 @@ def _load():
         "ud_tsdf_mesh": [P(UdTsdfMesh), vp],
         "ud_icp_linearize": [P(UdIcp), vp],
         "ud_icp_update": [P(UdIcp), vp],
+        "ud_depth_pyramid": [P(UdDepthPyramid), vp],
         "ud_eval_normals": [P(UdEvalNormals), vp, i64, vp],
         "ud_depth_minpool": [P(UdDepthMinPool), vp],
         "ud_resize_aa": [P(UdResizeAA), vp],
@@ -450,7 +457,7 @@ def _load():
     lib.ud_colorize_work_bytes.restype = i64
     lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
     lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency, None, UdTsdfIntegrate, UdTsdfPoints, UdTsdfRender, UdTsdfMesh, None, UdIcp]):
+    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency, None, UdTsdfIntegrate, UdTsdfPoints, UdTsdfRender, UdTsdfMesh, None, UdIcp, UdDepthPyramid]):
         if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35, 37, 40, 42 and 47 are not assigned: the library answers -1
             continue
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:

@@ -52,6 +52,7 @@ extern "C" int ud_struct_size(int which) {
     case 45: return (int)sizeof(UdTsdfRender);
     case 46: return (int)sizeof(UdTsdfMesh);
     case 48: return (int)sizeof(UdIcp);              // 47 stays unassigned (-1)
+    case 49: return (int)sizeof(UdDepthPyramid);
     default: return -1;
   }
 }

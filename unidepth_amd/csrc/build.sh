@@ -71,6 +71,10 @@ done
 # remap_taps.h), each per-pixel output with the bits of those launches run one after the other; the fp64 sums and the LDL^T / Cayley solve
 # round every operation once, so the numpy fp64 restatement and the host build of the tests have the solve's bits, same rule
 ( hipcc $FLAGS -ffp-contract=off "$@" -c icp.hip -o $BD/icp.o ) & pids+=($!)
+# pyramid: the bilateral filter's taps (difference, bin, weight, the two running sums, the division) and the gated 2 x 2 means are defined
+# operation by operation in fp32 in a fixed tap order (pyramid_point.h under this flag is what the numpy fp32 restatement and the host build
+# of the tests compute), same rule
+( hipcc $FLAGS -ffp-contract=off "$@" -c pyramid.hip -o $BD/pyramid.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c api.cpp -o $BD/api.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c program.cpp -o $BD/program.o ) & pids+=($!)
 ( hipcc $FLAGS -x hip -c rccl.cpp -o $BD/rccl.o ) & pids+=($!)

@@ -73,16 +73,46 @@ class TsdfVolume:
         _, valid, points, normals = self.render(camera, size, transform, near=near, far=far, step=step, min_weight=min_weight,
                                                 return_points=True, return_normals=True)
         E, stats = track_camera(depth, camera, points, normals, valid, camera, None, **kw)
-        A = invert_rigid(E)
-        if transform is None:
-            return A, stats
-        Bm = transform[..., :3, :].reshape(-1, 3, 4)
-        a = lambda i, j: A[:, i, j:j + 1]                            # noqa: E731
-        rows = []
-        for i in range(3):
-            row = (a(i, 0) * Bm[:, 0] + a(i, 1) * Bm[:, 1]) + a(i, 2) * Bm[:, 2]
-            rows.append(torch.cat([row[:, :3], row[:, 3:4] + a(i, 3)], dim=1))
-        return torch.stack(rows, dim=1).expand(B, 3, 4).contiguous(), stats
+        return _tracked_pose(E, transform, B), stats
+
+    def track_pyramid(self, depth, camera, size, transform, *, near, far, step=None, min_weight=1.0, levels=3, iters=(10, 5, 4), **kw):
+        """track, coarse to fine: the volume rendered at the prior pose once per level, at (H >> l, W >> l) through
+        pyramid.pyramid_cameras(camera, B, levels, device)[l], then pyramid.track_camera_pyramid(depth, those cameras, the renders, None,
+        iters=iters, **kw) from the identity (dist_tol is required; filter, gate, cos_tol, mask, weights, damping and min_count as there).
+        transform, size and the result: track's, composed the same way; stats fp64 [B,sum(iters),4] in execution order, coarsest level
+        first.  A level whose iters entry is 0 is not rendered."""
+        from .pyramid import pyramid_cameras, track_camera_pyramid
+        fn = "TsdfVolume.track_pyramid"
+        B = _check_volume(fn, self)[0]
+        H, W = _args.image_shape(fn, size, "size")
+        _args.levels(fn, levels, H, W, 4)
+        cams = pyramid_cameras(camera, B, levels, self.tsdf.device)
+        its = tuple(iters) if isinstance(iters, (tuple, list)) else iters
+        model_levels = []
+        for l in range(levels):
+            if isinstance(its, tuple) and len(its) == levels and its[l] == 0:
+                model_levels.append((None, None, None, cams[l]))
+                continue
+            _, valid, points, normals = self.render(cams[l], (H >> l, W >> l), transform, near=near, far=far, step=step, min_weight=min_weight,
+                                                    return_points=True, return_normals=True)
+            model_levels.append((points, normals, valid, cams[l]))
+        E, stats = track_camera_pyramid(depth, cams, model_levels, None, iters=iters, **kw)
+        return _tracked_pose(E, transform, B), stats
+
+
+def _tracked_pose(E, transform, B):
+    """track_camera's estimate E (frame camera -> prior camera) and the prior pose (volume -> camera) -> the frame's pose, volume -> camera:
+    invert_rigid(E) . transform, composed element-wise in fp32 in the order TsdfVolume.track documents"""
+    A = invert_rigid(E)
+    if transform is None:
+        return A
+    Bm = transform[..., :3, :].reshape(-1, 3, 4)
+    a = lambda i, j: A[:, i, j:j + 1]                            # noqa: E731
+    rows = []
+    for i in range(3):
+        row = (a(i, 0) * Bm[:, 0] + a(i, 1) * Bm[:, 1]) + a(i, 2) * Bm[:, 2]
+        rows.append(torch.cat([row[:, :3], row[:, 3:4] + a(i, 3)], dim=1))
+    return torch.stack(rows, dim=1).expand(B, 3, 4).contiguous()
 
 
 def _positive(fn, name, x):
