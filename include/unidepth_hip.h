@@ -1331,7 +1331,7 @@ int ud_calib_mfma_stream(const void* operands, int iters, int workgroups, void* 
 /* the same for v_mfma_f32_16x16x32_f16 (the GEMM family's instruction): workgroups of 8 waves, sink >= workgroups * 512 floats (round 6) */
 int ud_calib_mfma_stream16(const void* operands, int iters, int workgroups, void* sink, double* flop_out, void* stream);
 
-/* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0 ... UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
+/* library info; ud_struct_size(i): sizeof the i-th descriptor struct in declaration order (UdGemm = 0, UdLayerNorm = 1, UdAttention = 2, UdPreprocess = 3, UdRayEmbed = 4, UdUpsample2x = 5, UdResizeAC = 6, UdFinalize = 7, UdLinearF32 = 8, UdDwConv7 = 9, UdV1Op = 10, UdKnn = 11, UdExtractPatches = 12, UdCameraHead = 13, UdEvalDepth = 14, UdPointCloud = 15, UdMatchGt = 17,
  * UdColorize = 18, UdSplat = 20, UdDepthMinPool = 21, UdResizeAA = 23, UdEval3d = 25, UdReconstruct = 27, UdCameraProject = 28, UdSplatCamera = 29, UdCameraUnproject = 31, UdRemap = 33, UdOverlapMask = 34, UdWarpCamera = 36, UdNormals = 38, UdEvalNormals = 39, UdDepthConsistency = 41, UdTsdfIntegrate = 43, UdTsdfPoints = 44, UdTsdfRender = 45, UdTsdfMesh = 46, UdIcp = 48, UdDepthPyramid = 49; 16, 19, 22, 24, 26, 30, 32, 35, 37, 40, 42 and 47 are not assigned and answer -1 like every unknown
  * index) */
 int ud_version(void);

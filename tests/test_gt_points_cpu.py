@@ -2,10 +2,9 @@
 tools/make_golden_gt_points.py against the reference's own Camera.reconstruct arrays (tests/golden/gt_points.npz) at the measured bar,
 the conditions the generator promises (residual maxima outside [0.5e-3, 2e-3], the paths the cases must reach), the NOT normalised
 functions of csrc/camera_models.h compiled for the host (tests/recon_host/recon_host.cpp, a stand-alone program), the Python argument
-errors and the C-ABI's descriptor."""
+errors and the C-ABI's workspace query and argument checks."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -208,45 +207,6 @@ def test_argument_errors_without_gpu():
 
 
 # ---- C-ABI ------------------------------------------------------------------------------------------------------------------------
-
-def _header_fields():
-    """(name, ctypes type) of UdReconstruct's members, parsed from include/unidepth_hip.h."""
-    src = open(os.path.join(ROOT, "include", "unidepth_hip.h")).read()
-    body = re.search(r"typedef struct UdReconstruct \{(.*?)\} UdReconstruct;", src, re.S).group(1)
-    cap = int(re.search(r"#define UD_RECON_MAX_B (\d+)", src).group(1))
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        if "*" in decl:
-            fields.append((decl.split("*")[-1].strip(), C.c_void_p))
-        elif decl.startswith("long long"):
-            fields.append((decl.split()[-1], C.c_longlong))
-        elif decl.startswith("unsigned char"):
-            name, n = re.match(r"unsigned char (\w+)\[(\w+)\]", decl).groups()
-            assert n == "UD_RECON_MAX_B"
-            fields.append((name, C.c_ubyte * cap))
-        else:
-            assert decl.startswith("int "), decl
-            fields += [(n.strip(), C.c_int) for n in decl[4:].split(",")]
-    return src, cap, fields
-
-
-def test_descriptor_and_exports_match_the_binding():
-    from unidepth_amd import _lib
-    src, cap, fields = _header_fields()
-    assert cap == _lib.UD_RECON_MAX_B
-    assert [(n, t) for n, t in fields] == [(n, t) for n, t in _lib.UdReconstruct._fields_]
-    assert _lib.lib.ud_struct_size(27) == C.sizeof(_lib.UdReconstruct) and _lib.lib.ud_struct_size(26) == -1
-    assert _lib.lib.ud_version() >= 118
-    raw = C.CDLL(_lib.LIB_PATH)
-    for sym in ("ud_reconstruct", "ud_reconstruct_work_bytes"):
-        assert hasattr(raw, sym)
-    assert "int ud_reconstruct(const UdReconstruct* desc, void* stream);" in src
-    assert "long long ud_reconstruct_work_bytes(int B, int H, int W, int n_iterative);" in src
-    assert "UdReconstruct = 27" in src
-
 
 def test_work_bytes_and_c_abi_argument_checks():
     from unidepth_amd import _lib

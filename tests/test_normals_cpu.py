@@ -4,8 +4,6 @@ a stand-alone program) against the numpy fp32 restatement of tests/normals_commo
 test, the depth form through all six camera models, both known answers, the special values, the rgb bytes; the restatement of the metrics
 against a plain float64 formulation; the C-ABI's descriptors, every refusal of the entry points and the Python argument errors."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -139,40 +137,8 @@ def test_metric_restatement_special_cases():
 
 # ---- the C-ABI --------------------------------------------------------------------------------------------------------------------
 
-def _header_fields(name):
-    src = open(os.path.join(ROOT, "include", "unidepth_hip.h")).read()
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src, re.S).group(1)
-    caps = {k: int(v) for k, v in re.findall(r"#define (UD_RECON_MAX_B|UD_EVAL_NORMALS_MAX_T) (\d+)", src)}
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        if "*" in decl:
-            fields.append((decl.split("*")[-1].strip(), C.c_void_p))
-            continue
-        ctype = C.c_ubyte if decl.startswith("unsigned char") else C.c_int
-        assert decl.startswith("unsigned char ") or decl.startswith("int "), decl
-        for part in decl[len("unsigned char") if ctype is C.c_ubyte else 4:].split(","):
-            arr = re.match(r"\s*(\w+)\[(\w+)\]", part)
-            fields.append((arr.group(1), ctype * caps[arr.group(2)]) if arr else (part.strip(), ctype))
-    return src, fields
-
-
-def test_descriptors_and_exports_match_the_binding():
+def test_eval_normals_takes_at_most_eight_thresholds():
     from unidepth_amd import _lib
-    for name, st in (("UdNormals", _lib.UdNormals), ("UdEvalNormals", _lib.UdEvalNormals)):
-        src, fields = _header_fields(name)
-        assert fields == [(n, t) for n, t in st._fields_], name
-    assert _lib.lib.ud_struct_size(38) == C.sizeof(_lib.UdNormals) and _lib.lib.ud_struct_size(39) == C.sizeof(_lib.UdEvalNormals)
-    assert _lib.lib.ud_struct_size(37) == -1 and _lib.lib.ud_struct_size(40) == -1
-    assert "UdNormals = 38, UdEvalNormals = 39" in src
-    assert _lib.lib.ud_version() >= 123
-    raw = C.CDLL(_lib.LIB_PATH)
-    assert hasattr(raw, "ud_normals") and hasattr(raw, "ud_eval_normals") and hasattr(raw, "ud_eval_normals_work_bytes")
-    assert "int ud_normals(const UdNormals* desc, void* stream);" in src
-    assert "int ud_eval_normals(const UdEvalNormals* desc, void* workspace, long long bytes, void* stream);" in src
-    assert "long long ud_eval_normals_work_bytes(int B, int H, int W, int T);" in src
     assert _lib.UD_EVAL_NORMALS_MAX_T == 8
 
 

@@ -1,10 +1,9 @@
 """Point-cloud packing without a GPU (unidepth_amd/pointcloud.py, include/unidepth_hip.h UdPointCloud): the numpy restatement of
-tools/make_golden_pointcloud.py against the reference's own arrays (tests/golden/pointcloud.npz), the C-ABI's descriptor, argument
+tools/make_golden_pointcloud.py against the reference's own arrays (tests/golden/pointcloud.npz), the C-ABI's argument
 checks and workspace query, the PLY writers, and pack_points' argument errors."""
 import ctypes as C
 import importlib.util
 import os
-import re
 
 import numpy as np
 import pytest
@@ -68,37 +67,6 @@ def test_reference_rerun_reproduces_golden():
 
 
 # ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
-
-def _header_fields():
-    """(name, ctypes type) of UdPointCloud's members, parsed from include/unidepth_hip.h."""
-    with open(os.path.join(ROOT, "include", "unidepth_hip.h")) as f:
-        src = f.read()
-    body = re.search(r"typedef struct UdPointCloud \{(.*?)\} UdPointCloud;", src, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in (d.strip() for d in body.split(";")):
-        if not decl:
-            continue
-        m = re.match(r"(?:const\s+)?(unsigned char|long long|void|float|int)\s*(\*?)\s*(.*)$", decl, re.S)
-        assert m, decl
-        base, star, names = m.groups()
-        ct = C.c_void_p if star else {"long long": C.c_longlong, "int": C.c_int, "float": C.c_float}[base]
-        fields += [(n.strip(), ct) for n in names.split(",")]
-    return fields
-
-
-def test_descriptor_mirror_and_exports():
-    from unidepth_amd import _lib
-    assert _header_fields() == [(n, t) for n, t in _lib.UdPointCloud._fields_]
-    assert _lib.lib.ud_struct_size(15) == C.sizeof(_lib.UdPointCloud) and _lib.lib.ud_struct_size(16) == -1
-    assert _lib.lib.ud_version() >= 112
-    for sym in ("ud_pointcloud_pack", "ud_pointcloud_work_bytes"):
-        assert hasattr(_lib.lib, sym)
-    with open(os.path.join(ROOT, "include", "unidepth_hip.h")) as f:
-        src = f.read()
-    vals = dict(re.findall(r"(UD_PC_\w+) = (\d+)", re.search(r"enum \{ (UD_PC_MINCONF.*?) \};", src).group(1)))
-    assert {k: int(v) for k, v in vals.items()} == {k: getattr(_lib, k) for k in ("UD_PC_MINCONF", "UD_PC_RANGE", "UD_PC_EDGE", "UD_PC_FLIP_Y")}
-
 
 def test_pack_rejects_bad_descriptors_without_a_launch():
     """every refusal comes back before any HIP call: this runs on a machine without a GPU, the pointers are never followed"""

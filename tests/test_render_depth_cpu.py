@@ -1,10 +1,9 @@
 """Splatting without a GPU (unidepth_amd/reproject.py, include/unidepth_hip.h UdSplat / UdDepthMinPool): the numpy restatement of
-tools/make_golden_render_depth.py against the reference's own arrays (tests/golden/render_depth.npz), the C-ABI's descriptors, argument
+tools/make_golden_render_depth.py against the reference's own arrays (tests/golden/render_depth.npz), the C-ABI's argument
 checks and workspace query, and the argument errors of render_depth / project_points / downsample / reproject."""
 import ctypes as C
 import importlib.util
 import os
-import re
 
 import numpy as np
 import pytest
@@ -102,42 +101,6 @@ def test_reference_rerun_reproduces_golden():
 
 
 # ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
-
-def _header():
-    with open(os.path.join(ROOT, "include", "unidepth_hip.h")) as f:
-        return f.read()
-
-
-def _header_fields(struct):
-    """(name, ctypes type) of a descriptor's members, parsed from include/unidepth_hip.h."""
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), _header(), re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in (d.strip() for d in body.split(";")):
-        if not decl:
-            continue
-        m = re.match(r"(?:const\s+)?(unsigned char|long long|void|float|int)\s*(\*?)\s*(.*)$", decl, re.S)
-        assert m, decl
-        base, star, names = m.groups()
-        ct = C.c_void_p if star else {"long long": C.c_longlong, "int": C.c_int, "float": C.c_float}[base]
-        fields += [(n.strip(), ct) for n in names.split(",")]
-    return fields
-
-
-def test_descriptor_mirrors_and_exports():
-    from unidepth_amd import _lib
-    assert _header_fields("UdSplat") == [(n, t) for n, t in _lib.UdSplat._fields_]
-    assert _header_fields("UdDepthMinPool") == [(n, t) for n, t in _lib.UdDepthMinPool._fields_]
-    assert _lib.lib.ud_struct_size(20) == C.sizeof(_lib.UdSplat) and _lib.lib.ud_struct_size(21) == C.sizeof(_lib.UdDepthMinPool)
-    assert _lib.lib.ud_struct_size(16) == -1 and _lib.lib.ud_struct_size(19) == -1 and _lib.lib.ud_struct_size(22) == -1
-    assert _lib.lib.ud_version() >= 115
-    for sym in ("ud_splat", "ud_splat_work_bytes", "ud_depth_minpool"):
-        assert hasattr(_lib.lib, sym)
-    src = _header()
-    for enum, names in (("UD_SPLAT_NEAREST", ("UD_SPLAT_NEAREST", "UD_SPLAT_MEAN")), ("UD_SPLAT_TRUNC", ("UD_SPLAT_TRUNC", "UD_SPLAT_RANGE"))):
-        vals = dict(re.findall(r"(UD_SPLAT_\w+) = (\d+)", re.search(r"enum \{ (%s.*?) \};" % enum, src).group(1)))
-        assert {k: int(v) for k, v in vals.items()} == {k: getattr(_lib, k) for k in names}
-
 
 def test_splat_rejects_bad_descriptors_without_a_launch():
     """every refusal comes back before any HIP call: this runs on a machine without a GPU, the pointers are never followed"""

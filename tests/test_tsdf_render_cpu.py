@@ -1,7 +1,7 @@
 """tsdf_render without a GPU (unidepth_amd/tsdf.py, include/unidepth_hip.h UdTsdfRender): the per-ray function of csrc/tsdf_ray.h compiled for
 the host and run under the host sanitizers (tests/tsdf_render_host/tsdf_render_host.cpp, a stand-alone program), the clipped against the
 full scan inside the program and the full scan against the numpy restatement of tests/tsdf_render_common.py, bit for bit in every output;
-the conditions no scene may miss; the known answer and the special values; the C-ABI's descriptor, every refusal of the entry point and
+the conditions no scene may miss; the known answer and the special values; every refusal of the entry point and
 the Python argument errors."""
 import ctypes as C
 
@@ -11,7 +11,6 @@ import torch
 
 import tsdf_common as tc
 import tsdf_render_common as rc
-from test_tsdf_cpu import _header_fields
 
 F = np.float32
 
@@ -149,15 +148,6 @@ def test_host_special_values(hosts):
 
 
 # ---- C-ABI ------------------------------------------------------------------------------------------------------------------------
-
-def test_descriptor_and_export_match_the_binding():
-    from unidepth_amd import _lib
-    src, fields = _header_fields("UdTsdfRender")
-    assert fields == [(n, t) for n, t in _lib.UdTsdfRender._fields_]
-    assert _lib.lib.ud_struct_size(45) == C.sizeof(_lib.UdTsdfRender) and "UdTsdfRender = 45" in src
-    assert _lib.lib.ud_version() >= 126
-    assert hasattr(C.CDLL(_lib.LIB_PATH), "ud_tsdf_render") and "int ud_tsdf_render(const UdTsdfRender* desc, void* stream);" in src
-
 
 def test_every_refusal_of_render():
     """every refusal comes back before any HIP call: this runs without a GPU, on made-up addresses"""

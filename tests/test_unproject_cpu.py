@@ -1,11 +1,10 @@
 """unproject_camera without a GPU (unidepth_amd/unproject.py, include/unidepth_hip.h UdCameraUnproject): the numpy fp32 restatement of
 tools/make_golden_unproject.py against the reference's own Camera.unproject arrays and masks (tests/golden/unproject.npz) at the measured
 bars, the conditions the generator promises, the functions of csrc/camera_models.h compiled for the host and driven in the two-pass
-order under the host sanitizers (tests/unproj_host/unproj_host.cpp, a stand-alone program), the C-ABI's descriptor, every refusal of
+order under the host sanitizers (tests/unproj_host/unproj_host.cpp, a stand-alone program), the workspace query, every refusal of
 ud_camera_unproject and the Python argument errors."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -181,43 +180,6 @@ def test_header_functions_on_the_host_in_two_pass_order(unproj_host, name, b):
 
 
 # ---- C-ABI ------------------------------------------------------------------------------------------------------------------------
-
-def _header_fields():
-    src = open(os.path.join(ROOT, "include", "unidepth_hip.h")).read()
-    body = re.search(r"typedef struct UdCameraUnproject \{(.*?)\} UdCameraUnproject;", src, re.S).group(1)
-    cap = int(re.search(r"#define UD_RECON_MAX_B (\d+)", src).group(1))
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        if "*" in decl:
-            fields.append((decl.split("*")[-1].strip(), C.c_void_p))
-        elif decl.startswith("long long"):
-            fields += [(n.strip(), C.c_longlong) for n in decl[len("long long"):].split(",")]
-        elif decl.startswith("unsigned char"):
-            name, n = re.match(r"unsigned char (\w+)\[(\w+)\]", decl).groups()
-            assert n == "UD_RECON_MAX_B"
-            fields.append((name, C.c_ubyte * cap))
-        else:
-            assert decl.startswith("int "), decl
-            fields += [(n.strip(), C.c_int) for n in decl[4:].split(",")]
-    return src, fields
-
-
-def test_descriptor_and_exports_match_the_binding():
-    from unidepth_amd import _lib
-    src, fields = _header_fields()
-    assert fields == [(n, t) for n, t in _lib.UdCameraUnproject._fields_]
-    assert _lib.lib.ud_struct_size(31) == C.sizeof(_lib.UdCameraUnproject) and _lib.lib.ud_struct_size(32) == -1
-    assert _lib.lib.ud_version() >= 120
-    raw = C.CDLL(_lib.LIB_PATH)
-    for sym in ("ud_camera_unproject", "ud_camera_unproject_work_bytes"):
-        assert hasattr(raw, sym)
-    assert "int ud_camera_unproject(const UdCameraUnproject* desc, void* stream);" in src
-    assert "long long ud_camera_unproject_work_bytes(int B, int n_iterative);" in src
-    assert "UdCameraUnproject = 31" in src
-
 
 def test_work_bytes_and_every_refusal():
     """every refusal comes back before any HIP call: this runs without a GPU, on made-up addresses"""

@@ -1,10 +1,9 @@
 """Colourising without a GPU (unidepth_amd/visualization.py, include/unidepth_hip.h UdColorize): the numpy restatement of
 tools/make_golden_colorize.py and the host colorize / image_grid against the reference's own bytes (tests/golden/colorize.npz), the
-generated colormap tables, save_png, the C-ABI's descriptor, refusals and workspace query, and the Python argument errors."""
+generated colormap tables, save_png, the C-ABI's refusals and workspace query, and the Python argument errors."""
 import ctypes as C
 import importlib.util
 import os
-import re
 import struct
 import zlib
 
@@ -169,45 +168,6 @@ def test_save_png_roundtrip(tmp_path, H, W):
 
 
 # ---- C-ABI ---------------------------------------------------------------------------------------------------------------------------
-
-_CT = {"long long": C.c_longlong, "int": C.c_int, "float": C.c_float}
-
-
-def _header_fields(struct_name, nested=None):
-    """(name, ctypes type) of a descriptor's members, parsed from include/unidepth_hip.h."""
-    with open(os.path.join(ROOT, "include", "unidepth_hip.h")) as f:
-        src = f.read()
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct_name, struct_name), src, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in (d.strip() for d in body.split(";")):
-        if not decl:
-            continue
-        m = re.match(r"UdColorPanel\s+(\w+)\[UD_COLORIZE_MAX_PANELS\]$", decl)
-        if m:
-            fields.append((m.group(1), nested))
-            continue
-        m = re.match(r"(?:const\s+)?(unsigned char|long long|void|float|int)\s*(\*?)\s*(.*)$", decl, re.S)
-        assert m, decl
-        base, star, names = m.groups()
-        fields += [(n.strip(), C.c_void_p if star else _CT[base]) for n in names.split(",")]
-    return fields
-
-
-def test_descriptor_mirror_and_exports():
-    from unidepth_amd import _lib
-    assert _header_fields("UdColorPanel") == [(n, t) for n, t in _lib.UdColorPanel._fields_]
-    assert _header_fields("UdColorize", _lib.UdColorPanel * 4) == [(n, t) for n, t in _lib.UdColorize._fields_]
-    assert _lib.lib.ud_struct_size(18) == C.sizeof(_lib.UdColorize) and _lib.lib.ud_struct_size(19) == -1
-    assert _lib.lib.ud_version() >= 114
-    for sym in ("ud_colorize", "ud_colorize_work_bytes"):
-        assert hasattr(_lib.lib, sym)
-    with open(os.path.join(ROOT, "include", "unidepth_hip.h")) as f:
-        src = f.read()
-    vals = {k: int(v) for k, v in re.findall(r"(UD_CZ_\w+) = (\d+)", src)}
-    assert vals == {k: getattr(_lib, k) for k in ("UD_CZ_NONE", "UD_CZ_MAP", "UD_CZ_AREL", "UD_CZ_RGB", "UD_CZ_AUTO_LO", "UD_CZ_AUTO_HI", "UD_CZ_CHW")}
-    assert int(re.search(r"#define UD_COLORIZE_MAX_PANELS (\d+)", src).group(1)) == _lib.UD_COLORIZE_MAX_PANELS == 4
-
 
 def test_colorize_rejects_bad_descriptors_without_a_launch():
     """every refusal comes back before any HIP call: this runs on a machine without a GPU, the pointers are never followed"""

@@ -4,8 +4,6 @@ the chain of the separate per-point functions of camera_models.h and remap_taps.
 source type and transform of the GPU tests' cases, on the special values and on the known answer; the C-ABI's descriptor, every refusal
 of the entry point and the Python argument errors.  Shared helpers: tests/warp_common.py."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -98,41 +96,11 @@ def test_host_known_answer(warp_host):
 
 # ---- C-ABI ------------------------------------------------------------------------------------------------------------------------
 
-def _header_fields():
-    src = open(os.path.join(ROOT, "include", "unidepth_hip.h")).read()
-    body = re.search(r"typedef struct UdWarpCamera \{(.*?)\} UdWarpCamera;", src, re.S).group(1)
-    cap = int(re.search(r"#define UD_RECON_MAX_B (\d+)", src).group(1))
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        if "*" in decl:
-            fields.append((decl.split("*")[-1].strip(), C.c_void_p))
-        elif decl.startswith("long long"):
-            fields += [(n.strip(), C.c_longlong) for n in decl[len("long long"):].split(",")]
-        elif decl.startswith("unsigned char"):                               # the two model arrays, one declaration
-            for part in decl[len("unsigned char"):].split(","):
-                name, n = re.match(r"\s*(\w+)\[(\w+)\]", part).groups()
-                assert n == "UD_RECON_MAX_B"
-                fields.append((name, C.c_ubyte * cap))
-        else:
-            assert decl.startswith("int "), decl
-            fields += [(n.strip(), C.c_int) for n in decl[4:].split(",")]
-    return src, fields
-
-
-def test_descriptor_and_exports_match_the_binding():
+def test_warp_descriptor_ends_with_the_model_arrays_and_has_no_float_field():
     from unidepth_amd import _lib
-    src, fields = _header_fields()
-    assert fields == [(n, t) for n, t in _lib.UdWarpCamera._fields_]
+    fields = _lib.UdWarpCamera._fields_
     assert [n for n, _ in fields[-2:]] == ["model_dst", "model_src"]
     assert all(t in (C.c_void_p, C.c_longlong, C.c_int) for _, t in fields[:-2])
-    assert _lib.lib.ud_struct_size(36) == C.sizeof(_lib.UdWarpCamera) and _lib.lib.ud_struct_size(35) == -1
-    assert "UdWarpCamera = 36" in src
-    assert _lib.lib.ud_version() >= 122
-    assert hasattr(C.CDLL(_lib.LIB_PATH), "ud_warp_camera")
-    assert "int ud_warp_camera(const UdWarpCamera* desc, void* stream);" in src
 
 
 def test_every_refusal():

@@ -330,136 +330,138 @@ class UdFinalize(C.Structure):
                 ("Hp", i32), ("Wp", i32), ("pad_l", i32), ("pad_t", i32), ("Ho", i32), ("Wo", i32), ("mode", i32)]
 
 
+P = C.POINTER
+# argument types of every function include/unidepth_hip.h declares; the return type is i32 unless RESTYPE says otherwise
+SIG = {
+    "ud_gemm_f16": [P(UdGemm), vp],
+    "ud_gemm_pick": [P(UdGemm)],
+    "ud_gemm_kernel_name": [P(UdGemm), C.c_char_p, i32],
+    "ud_layernorm_f32_f16": [P(UdLayerNorm), vp],
+    "ud_rccl_unique_id": [vp],
+    "ud_rccl_init": [vp, i32, i32],
+    "ud_rccl_allgather_outputs": [vp, vp, C.c_size_t, i32, vp],
+    "ud_rccl_finalize": [],
+    "ud_attention_f16": [P(UdAttention), vp],
+    "ud_row_stats_finalize": [vp, vp, i32, i32, i32, f32, vp],
+    "ud_program_add_row_stats_finalize": [vp, vp, vp, i32, i32, i32, f32],
+    "ud_linear_f32": [P(UdLinearF32), vp],
+    "ud_attention_small_f32": [vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    "ud_program_add_linear_f32": [vp, P(UdLinearF32)],
+    "ud_camera_head_f32": [P(UdCameraHead), vp],
+    "ud_camera_head_supported": [P(UdCameraHead)],
+    "ud_program_add_camera_head": [vp, P(UdCameraHead)],
+    "ud_program_add_attention_small_f32": [vp, vp, vp, vp, i32, i32, i32, i32, f32],
+    "ud_preprocess_patches": [P(UdPreprocess), vp],
+    "ud_fill_rows_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "ud_camera_intrinsics": [vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp],
+    "ud_rays_from_kinv": [vp, vp, i32, i32, i32, i32, vp],
+    "ud_rays_from_camera": [vp, vp, vp, i32, i32, i32, vp],
+    "ud_ray_embed": [P(UdRayEmbed), vp],
+    "ud_upsample2x_nhwc": [P(UdUpsample2x), vp],
+    "ud_resize_ac_nhwc_f16": [P(UdResizeAC), vp],
+    "ud_finalize_outputs": [P(UdFinalize), vp],
+    "ud_nhwc_to_nchw_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "ud_program_destroy": [vp],
+    "ud_program_size": [vp],
+    "ud_program_add_gemm": [vp, P(UdGemm)],
+    "ud_program_add_layernorm": [vp, P(UdLayerNorm)],
+    "ud_program_add_attention": [vp, P(UdAttention)],
+    "ud_program_add_preprocess": [vp, P(UdPreprocess)],
+    "ud_program_add_fill_rows": [vp, vp, vp, i32, i32, i32, i32, i32],
+    "ud_program_add_camera_intrinsics": [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32],
+    "ud_program_add_rays": [vp, vp, vp, i32, i32, i32, i32],
+    "ud_program_add_rays_camera": [vp, vp, vp, vp, i32, i32, i32],
+    "ud_program_add_ray_embed": [vp, P(UdRayEmbed)],
+    "ud_program_add_upsample2x": [vp, P(UdUpsample2x)],
+    "ud_program_add_resize_ac": [vp, P(UdResizeAC)],
+    "ud_program_add_finalize": [vp, P(UdFinalize)],
+    "ud_program_add_nhwc_to_nchw": [vp, vp, vp, i32, i32, i32, i32, i32],
+    "ud_dwconv7_nhwc_f32": [P(UdDwConv7), vp],
+    "ud_layernorm_patchify2": [vp, vp, i32, i32, i32, i32, i32, f32, vp],
+    "ud_patchify4_nchw": [vp, vp, i32, i32, i32, i32, vp],
+    "ud_max_f32": [vp, vp, i64, i32, vp],
+    "ud_spatial_mean_f32": [vp, vp, i32, i32, i32, i32, vp],
+    "ud_program_add_dwconv7": [vp, P(UdDwConv7)],
+    "ud_program_add_layernorm_patchify2": [vp, vp, vp, i32, i32, i32, i32, i32, f32],
+    "ud_program_add_patchify4": [vp, vp, vp, i32, i32, i32, i32],
+    "ud_program_add_max": [vp, vp, vp, i64, i32],
+    "ud_program_add_spatial_mean": [vp, vp, vp, i32, i32, i32, i32],
+    "ud_v1_op": [P(UdV1Op), vp],
+    "ud_program_add_v1_op": [vp, P(UdV1Op)],
+    "ud_knn_points": [P(UdKnn), vp],
+    "ud_knn_split": [P(UdKnn)],
+    "ud_extract_patches": [P(UdExtractPatches), vp],
+    "ud_eval_depth": [P(UdEvalDepth), vp],
+    "ud_eval_3d": [P(UdEval3d), vp],
+    "ud_reconstruct": [P(UdReconstruct), vp],
+    "ud_pointcloud_pack": [P(UdPointCloud), vp],
+    "ud_match_gt": [P(UdMatchGt), vp],
+    "ud_colorize": [P(UdColorize), vp],
+    "ud_splat": [P(UdSplat), vp],
+    "ud_splat_camera": [P(UdSplatCamera), vp],
+    "ud_camera_project": [P(UdCameraProject), vp],
+    "ud_camera_unproject": [P(UdCameraUnproject), vp],
+    "ud_remap": [P(UdRemap), vp],
+    "ud_overlap_mask": [P(UdOverlapMask), vp],
+    "ud_warp_camera": [P(UdWarpCamera), vp],
+    "ud_normals": [P(UdNormals), vp],
+    "ud_depth_consistency": [P(UdDepthConsistency), vp],
+    "ud_tsdf_integrate": [P(UdTsdfIntegrate), vp],
+    "ud_tsdf_points": [P(UdTsdfPoints), vp],
+    "ud_tsdf_render": [P(UdTsdfRender), vp],
+    "ud_tsdf_mesh": [P(UdTsdfMesh), vp],
+    "ud_icp_linearize": [P(UdIcp), vp],
+    "ud_icp_update": [P(UdIcp), vp],
+    "ud_depth_pyramid": [P(UdDepthPyramid), vp],
+    "ud_eval_normals": [P(UdEvalNormals), vp, i64, vp],
+    "ud_depth_minpool": [P(UdDepthMinPool), vp],
+    "ud_resize_aa": [P(UdResizeAA), vp],
+    "ud_program_run": [vp, i32, i32, vp],
+    "ud_calib_mfma_stream": [vp, i32, i32, vp, P(C.c_double), vp],
+    "ud_calib_mfma_stream16": [vp, i32, i32, vp, P(C.c_double), vp],
+    "ud_version": [],
+    "ud_struct_size": [i32],
+    "ud_eval_depth_work_bytes": [i32, i32, i32],
+    "ud_eval_3d_work_bytes": [i32, i32, i32, i32],
+    "ud_eval_normals_work_bytes": [i32, i32, i32, i32],
+    "ud_reconstruct_work_bytes": [i32, i32, i32, i32],
+    "ud_camera_unproject_work_bytes": [i32, i32],
+    "ud_pointcloud_work_bytes": [i32, i32, i32],
+    "ud_tsdf_points_work_bytes": [i32, i32, i32, i32],
+    "ud_tsdf_mesh_work_bytes": [i32, i32, i32, i32],
+    "ud_icp_workspace_bytes": [i32, i32, i32],
+    "ud_colorize_work_bytes": [i32, i32, i32],
+    "ud_splat_work_bytes": [i32, i32, i32],
+    "ud_program_create": [],
+    "ud_last_error": [],
+}
+RESTYPE = {"ud_program_destroy": None, "ud_program_create": vp, "ud_last_error": C.c_char_p}
+RESTYPE.update(dict.fromkeys((
+    "ud_eval_depth_work_bytes", "ud_eval_3d_work_bytes", "ud_eval_normals_work_bytes", "ud_reconstruct_work_bytes",
+    "ud_camera_unproject_work_bytes", "ud_pointcloud_work_bytes", "ud_tsdf_points_work_bytes", "ud_tsdf_mesh_work_bytes",
+    "ud_icp_workspace_bytes", "ud_colorize_work_bytes", "ud_splat_work_bytes"), i64))
+
+# ud_struct_size(i) of the library; the numbers missing here are not assigned: the library answers -1
+STRUCT_INDEX = {
+    0: UdGemm, 1: UdLayerNorm, 2: UdAttention, 3: UdPreprocess, 4: UdRayEmbed, 5: UdUpsample2x, 6: UdResizeAC, 7: UdFinalize, 8: UdLinearF32,
+    9: UdDwConv7, 10: UdV1Op, 11: UdKnn, 12: UdExtractPatches, 13: UdCameraHead, 14: UdEvalDepth, 15: UdPointCloud, 17: UdMatchGt, 18: UdColorize,
+    20: UdSplat, 21: UdDepthMinPool, 23: UdResizeAA, 25: UdEval3d, 27: UdReconstruct, 28: UdCameraProject, 29: UdSplatCamera, 31: UdCameraUnproject,
+    33: UdRemap, 34: UdOverlapMask, 36: UdWarpCamera, 38: UdNormals, 39: UdEvalNormals, 41: UdDepthConsistency, 43: UdTsdfIntegrate, 44: UdTsdfPoints,
+    45: UdTsdfRender, 46: UdTsdfMesh, 48: UdIcp, 49: UdDepthPyramid,
+}
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
             f"{LIB_PATH} not found: the HIP kernel library is not built. Run `python -c 'import __graft_entry__ as g; "
             "g.build()'` or unidepth_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    P = C.POINTER
-    sig = {
-        "ud_gemm_f16": [P(UdGemm), vp],
-        "ud_gemm_pick": [P(UdGemm)],
-        "ud_gemm_kernel_name": [P(UdGemm), C.c_char_p, i32],
-        "ud_layernorm_f32_f16": [P(UdLayerNorm), vp],
-        "ud_rccl_unique_id": [vp],
-        "ud_rccl_init": [vp, i32, i32],
-        "ud_rccl_allgather_outputs": [vp, vp, C.c_size_t, i32, vp],
-        "ud_rccl_finalize": [],
-        "ud_attention_f16": [P(UdAttention), vp],
-        "ud_row_stats_finalize": [vp, vp, i32, i32, i32, f32, vp],
-        "ud_program_add_row_stats_finalize": [vp, vp, vp, i32, i32, i32, f32],
-        "ud_linear_f32": [P(UdLinearF32), vp],
-        "ud_attention_small_f32": [vp, vp, vp, i32, i32, i32, i32, f32, vp],
-        "ud_program_add_linear_f32": [vp, P(UdLinearF32)],
-        "ud_camera_head_f32": [P(UdCameraHead), vp],
-        "ud_camera_head_supported": [P(UdCameraHead)],
-        "ud_program_add_camera_head": [vp, P(UdCameraHead)],
-        "ud_program_add_attention_small_f32": [vp, vp, vp, vp, i32, i32, i32, i32, f32],
-        "ud_preprocess_patches": [P(UdPreprocess), vp],
-        "ud_fill_rows_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
-        "ud_camera_intrinsics": [vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp],
-        "ud_rays_from_kinv": [vp, vp, i32, i32, i32, i32, vp],
-        "ud_rays_from_camera": [vp, vp, vp, i32, i32, i32, vp],
-        "ud_ray_embed": [P(UdRayEmbed), vp],
-        "ud_upsample2x_nhwc": [P(UdUpsample2x), vp],
-        "ud_resize_ac_nhwc_f16": [P(UdResizeAC), vp],
-        "ud_finalize_outputs": [P(UdFinalize), vp],
-        "ud_nhwc_to_nchw_f32": [vp, vp, i32, i32, i32, i32, i32, vp],
-        "ud_program_destroy": [vp],
-        "ud_program_size": [vp],
-        "ud_program_add_gemm": [vp, P(UdGemm)],
-        "ud_program_add_layernorm": [vp, P(UdLayerNorm)],
-        "ud_program_add_attention": [vp, P(UdAttention)],
-        "ud_program_add_preprocess": [vp, P(UdPreprocess)],
-        "ud_program_add_fill_rows": [vp, vp, vp, i32, i32, i32, i32, i32],
-        "ud_program_add_camera_intrinsics": [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32],
-        "ud_program_add_rays": [vp, vp, vp, i32, i32, i32, i32],
-        "ud_program_add_rays_camera": [vp, vp, vp, vp, i32, i32, i32],
-        "ud_program_add_ray_embed": [vp, P(UdRayEmbed)],
-        "ud_program_add_upsample2x": [vp, P(UdUpsample2x)],
-        "ud_program_add_resize_ac": [vp, P(UdResizeAC)],
-        "ud_program_add_finalize": [vp, P(UdFinalize)],
-        "ud_program_add_nhwc_to_nchw": [vp, vp, vp, i32, i32, i32, i32, i32],
-        "ud_dwconv7_nhwc_f32": [P(UdDwConv7), vp],
-        "ud_layernorm_patchify2": [vp, vp, i32, i32, i32, i32, i32, f32, vp],
-        "ud_patchify4_nchw": [vp, vp, i32, i32, i32, i32, vp],
-        "ud_max_f32": [vp, vp, i64, i32, vp],
-        "ud_spatial_mean_f32": [vp, vp, i32, i32, i32, i32, vp],
-        "ud_program_add_dwconv7": [vp, P(UdDwConv7)],
-        "ud_program_add_layernorm_patchify2": [vp, vp, vp, i32, i32, i32, i32, i32, f32],
-        "ud_program_add_patchify4": [vp, vp, vp, i32, i32, i32, i32],
-        "ud_program_add_max": [vp, vp, vp, i64, i32],
-        "ud_program_add_spatial_mean": [vp, vp, vp, i32, i32, i32, i32],
-        "ud_v1_op": [P(UdV1Op), vp],
-        "ud_program_add_v1_op": [vp, P(UdV1Op)],
-        "ud_knn_points": [P(UdKnn), vp],
-        "ud_knn_split": [P(UdKnn)],
-        "ud_extract_patches": [P(UdExtractPatches), vp],
-        "ud_eval_depth": [P(UdEvalDepth), vp],
-        "ud_eval_3d": [P(UdEval3d), vp],
-        "ud_reconstruct": [P(UdReconstruct), vp],
-        "ud_pointcloud_pack": [P(UdPointCloud), vp],
-        "ud_match_gt": [P(UdMatchGt), vp],
-        "ud_colorize": [P(UdColorize), vp],
-        "ud_splat": [P(UdSplat), vp],
-        "ud_splat_camera": [P(UdSplatCamera), vp],
-        "ud_camera_project": [P(UdCameraProject), vp],
-        "ud_camera_unproject": [P(UdCameraUnproject), vp],
-        "ud_remap": [P(UdRemap), vp],
-        "ud_overlap_mask": [P(UdOverlapMask), vp],
-        "ud_warp_camera": [P(UdWarpCamera), vp],
-        "ud_normals": [P(UdNormals), vp],
-        "ud_depth_consistency": [P(UdDepthConsistency), vp],
-        "ud_tsdf_integrate": [P(UdTsdfIntegrate), vp],
-        "ud_tsdf_points": [P(UdTsdfPoints), vp],
-        "ud_tsdf_render": [P(UdTsdfRender), vp],
-        "ud_tsdf_mesh": [P(UdTsdfMesh), vp],
-        "ud_icp_linearize": [P(UdIcp), vp],
-        "ud_icp_update": [P(UdIcp), vp],
-        "ud_depth_pyramid": [P(UdDepthPyramid), vp],
-        "ud_eval_normals": [P(UdEvalNormals), vp, i64, vp],
-        "ud_depth_minpool": [P(UdDepthMinPool), vp],
-        "ud_resize_aa": [P(UdResizeAA), vp],
-        "ud_program_run": [vp, i32, i32, vp],
-        "ud_calib_mfma_stream": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
-        "ud_calib_mfma_stream16": [vp, i32, i32, vp, C.POINTER(C.c_double), vp],
-        "ud_version": [],
-        "ud_struct_size": [i32],
-    }
-    for name, args in sig.items():
+    for name, args in SIG.items():
         fn = getattr(lib, name)
         fn.argtypes = args
-        fn.restype = None if name == "ud_program_destroy" else i32
-    lib.ud_program_create.argtypes = []
-    lib.ud_program_create.restype = vp
-    lib.ud_last_error.argtypes = []
-    lib.ud_last_error.restype = C.c_char_p
-    lib.ud_eval_depth_work_bytes.argtypes = [i32, i32, i32]
-    lib.ud_eval_depth_work_bytes.restype = i64
-    lib.ud_eval_3d_work_bytes.argtypes = [i32, i32, i32, i32]
-    lib.ud_eval_3d_work_bytes.restype = i64
-    lib.ud_eval_normals_work_bytes.argtypes = [i32, i32, i32, i32]
-    lib.ud_eval_normals_work_bytes.restype = i64
-    lib.ud_reconstruct_work_bytes.argtypes = [i32, i32, i32, i32]
-    lib.ud_reconstruct_work_bytes.restype = i64
-    lib.ud_camera_unproject_work_bytes.argtypes = [i32, i32]
-    lib.ud_camera_unproject_work_bytes.restype = i64
-    lib.ud_pointcloud_work_bytes.argtypes = [i32, i32, i32]
-    lib.ud_pointcloud_work_bytes.restype = i64
-    lib.ud_tsdf_points_work_bytes.argtypes = [i32, i32, i32, i32]
-    lib.ud_tsdf_points_work_bytes.restype = i64
-    lib.ud_tsdf_mesh_work_bytes.argtypes = [i32, i32, i32, i32]
-    lib.ud_tsdf_mesh_work_bytes.restype = i64
-    lib.ud_icp_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.ud_icp_workspace_bytes.restype = i64
-    lib.ud_colorize_work_bytes.argtypes = [i32, i32, i32]
-    lib.ud_colorize_work_bytes.restype = i64
-    lib.ud_splat_work_bytes.argtypes = [i32, i32, i32]
-    lib.ud_splat_work_bytes.restype = i64
-    for i, st in enumerate([UdGemm, UdLayerNorm, UdAttention, UdPreprocess, UdRayEmbed, UdUpsample2x, UdResizeAC, UdFinalize, UdLinearF32, UdDwConv7, UdV1Op, UdKnn, UdExtractPatches, UdCameraHead, UdEvalDepth, UdPointCloud, None, UdMatchGt, UdColorize, None, UdSplat, UdDepthMinPool, None, UdResizeAA, None, UdEval3d, None, UdReconstruct, UdCameraProject, UdSplatCamera, None, UdCameraUnproject, None, UdRemap, UdOverlapMask, None, UdWarpCamera, None, UdNormals, UdEvalNormals, None, UdDepthConsistency, None, UdTsdfIntegrate, UdTsdfPoints, UdTsdfRender, UdTsdfMesh, None, UdIcp, UdDepthPyramid]):
-        if st is None:                                  # indices 16, 19, 22, 24, 26, 30, 32, 35, 37, 40, 42 and 47 are not assigned: the library answers -1
-            continue
+        fn.restype = RESTYPE.get(name, i32)
+    for i, st in STRUCT_INDEX.items():
         # a library whose descriptors differ from this mirror in ANY way is a hard error (A/B runs rebuild both arms from one tree:
         # an older .so would read the appended fields -- a_wrap, row_stats_* -- as garbage or not at all)
         if lib.ud_struct_size(i) != C.sizeof(st):
